@@ -14,7 +14,8 @@ projector) -> splice -> decoder prefill (1087 positions) -> 127 decode steps wit
                                                         ONE TP = N job — image tower data parallel over the ranks, packed prefill, N sequences decoding together —
                                                         generated tokens of all N requests / wall second; `strong_single_request` = one request over TP = N (the
                                                         latency view), `replicas` = N independent one-GPU replicas, both in the same line.  DESIGN.md §4 "Multi-GPU")
-Extra objects on the JSON line (measured in the same process after the timed region, HIP events on the launch stream):
+`--dump-outputs DIR` writes the ids the last timed step returned to DIR/output_ids.npy (inputs are seeded: two builds compare output for output).
+Extra objects on the JSON line, with `--full` only (measured in the same process after the timed region, HIP events on the launch stream; null without it):
   roofline          dominant kernel of the step by time = decode weight-streaming GEMV family (HBM-bound)
   roofline_prefill  dominant prefill kernel = MFMA GEMM family (MFMA-bound; north_star's 40 % target)
   cpu_baseline      kind "reference": the reference's OWN model files (byte code in oracle/_ref, oracle/ref_shim.py) run on this box's host cores on a bounded
@@ -68,7 +69,27 @@ def parse():
     ap.add_argument("--no-parity-probe", action="store_true", help="skip the live parity probe (the fp32 verification engine on the same bf16-rounded weights: "
                                                                   "last-position prefill logits and the first greedy ids of the timed request)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc passes that measure roofline.traffic")
+    ap.add_argument("--full", action="store_true", help="config2: after the timed steps also measure everything beside the headline (phase split, in-situ kernel profile and "
+                                                        "rooflines, live PMC traffic, serving batch, live parity probe, TP projection, CPU baseline; N > 1: replicas). "
+                                                        "Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last timed step to DIR/<name>.npy "
+                                                                        "(integers as float64, floats as float32; at most 64 MB)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array; integer ids as float64 (exact), everything else as float32.  The inputs are seeded, so two builds
+    run with the same arguments can be compared output for output."""
+    import numpy as np
+    out = {k: (v.detach().float() if v.is_floating_point() else v.detach().double()).cpu().numpy() for k, v in arrays.items()}
+    total = sum(x.nbytes for x in out.values())
+    assert total <= DUMP_LIMIT_BYTES, f"outputs of {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte dump limit"
+    os.makedirs(path, exist_ok=True)
+    for k, x in out.items():
+        np.save(os.path.join(path, k + ".npy"), x)
 
 
 def flops_prefill(cfg, T, n_images):
@@ -598,6 +619,7 @@ def run_config5(a, model, cfg, synth, dev, dtype, barrier, world, rank, share, b
     The backward kernels are parity-first (csrc/train.hip; the attention backward of 16-bit models runs on the matrix cores since round 3, csrc/attn_bwd.hip;
     dgrad / wgrad still transpose their operands onto the forward GEMM): the default micro-batch is small
     (--train-batch 1 --train-seq 1024); the number is a first measurement of a correct step, not a tuned one."""
+    import numpy as np
     from synthetic import build as harness
     from llava_mi355x.train import TrainStep
     group = None
@@ -642,6 +664,10 @@ def run_config5(a, model, cfg, synth, dev, dtype, barrier, world, rank, share, b
     barrier()
     dt = time.perf_counter() - t0
     losses.append(float(loss.item()))
+    if a.dump_outputs and rank == 0:
+        # before the phase split below, which steps the optimiser again: the loss, the label count and a fixed sample of the parameters the last step updated
+        sample = torch.from_numpy(np.random.default_rng(0).choice(ts.flat_p.numel(), size=min(1 << 20, ts.flat_p.numel()), replace=False)).to(dev)
+        dump_outputs(a.dump_outputs, {"loss": loss.reshape(1), "counted_labels": count.reshape(1), "params_sample": ts.flat_p[sample]})
     if world > 1:
         import torch.distributed as dist
         tt = torch.tensor([dt], device="cpu" if share else dev, dtype=torch.float64)
@@ -718,6 +744,8 @@ def run_config3(a, model, cfg, synth, dev, dtype, barrier, world, rank, share, b
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     same = all(torch.equal(x, y) for x, y in zip(first, last))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"output_ids": torch.stack([o.reshape(-1) for o in last])})
     # phase split: the 8 chunked prefills, then 127 batched decode steps (event-bracketed replay)
     e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
     barrier()
@@ -841,7 +869,292 @@ def main():
     ms_per_step = dt / a.steps * 1e3
     value = a.new_tokens * a.steps / dt
 
-    # ---- phase split + per-kernel durations: one profiled replay of the same step (HIP events on the launch stream) ----
+    # ---- --full: phase split + per-kernel durations from profiled replays of the same step (HIP events on the launch stream) ----
+    prefill_ms = decode_ms = roof = roof_p = breakdown = None
+    if a.full:
+        prefill_ms, decode_ms, roof, roof_p, breakdown = profile_request(a, model, cfg, dev, ids, pix, T, world, rank, barrier, step)
+
+    # ---- N > 1: the weak-scaling job — N requests (one per GPU, own image + own prompt) as ONE tensor-parallel job: the tower data parallel over the
+    #      images, packed prefill, the N sequences decoding together (model.generate_batch; every rank runs the same plan).  This is the workload the
+    #      line's `value` is quoted on at N > 1 (DESIGN.md §4 "Multi-GPU"); the single request over TP = N stays beside it as `strong_single_request`
+    weak, last_w = None, None
+    if world > 1 and not a.no_weak:
+        import torch.distributed as dist
+        try:
+            pw, iw = weak_job_inputs(cfg, dev, dtype, world, a.prompt_len)
+
+            def step_w():
+                o = model.generate_batch(pw, iw, max_new_tokens=a.new_tokens, eos_token_id=-1, run_ahead=a.new_tokens, prefill_chunk=512, capacity=world)
+                assert all(x.numel() == a.prompt_len + a.new_tokens for x in o)
+                return o
+
+            first_w = None
+            for _ in range(max(1, min(a.warmup, 2))):
+                first_w = step_w()
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                last_w = step_w()
+            barrier()
+            dtw = time.perf_counter() - t0
+            ttw = torch.tensor([dtw], device="cpu" if share else dev, dtype=torch.float64)
+            dist.all_reduce(ttw, op=dist.ReduceOp.MAX)
+            dtw = float(ttw.item())
+            weak = {"what": f"{world} requests, one per GPU, as one TP = {world} job: image tower data parallel over the ranks + feature all-gather, packed prefill in pieces "
+                            f"of {world} x 512 rows, {world} sequences decoding together", "requests": world, "scaling": "weak",
+                    "value": world * a.new_tokens * a.steps / dtw, "ms_per_step": dtw / a.steps * 1e3,
+                    "tower_sharded": bool(model.tower_is_sharded(world)),
+                    "greedy_ids_identical_across_steps": bool(all(torch.equal(x, y) for x, y in zip(first_w, last_w)))}
+        except Exception as ex:  # noqa: BLE001 — the line keeps the single-request measurement as its value and says why
+            weak = {"error": repr(ex)}
+
+    if a.dump_outputs and rank == 0:
+        # the ids the caller of the timed path received in the last timed step: the weak job's N sequences when it is the headline, else the one request
+        dump_outputs(a.dump_outputs, {"output_ids": torch.stack([x.reshape(-1) for x in last_w]) if weak and "value" in weak else outs[-1]})
+
+    # ---- N > 1: the same N GPUs as N independent replicas (SURVEY §8e "data-parallel serving fallback": one full model per GPU, one
+    #      request each, no collective) — reported next to the tensor-parallel `value`, never instead of it
+    replicas = None
+    one_gpu_same_job = None
+    if a.full and world > 1 and not a.no_replicas:
+        import torch.distributed as dist
+        del outs
+        full = harness.build_model(cfg, dtype=dtype, seed=0, device_rng=True, device=dev, tp_rank=0, tp_world=1, max_position=2048)
+        ids_r = torch.from_numpy(synth.make_prompt(cfg, a.prompt_len, image_positions=(35,), seed=2 + rank))[None].to(dev)
+
+        def step_r():
+            return full.generate(inputs=ids_r, images=pix, do_sample=False, max_new_tokens=a.new_tokens, eos_token_id=-1, run_ahead=a.new_tokens)
+
+        for _ in range(max(1, a.warmup)):
+            step_r()
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            step_r()
+        barrier()
+        dtr = time.perf_counter() - t0
+        ttr = torch.tensor([dtr], device="cpu" if share else dev, dtype=torch.float64)
+        dist.all_reduce(ttr, op=dist.ReduceOp.MAX)
+        dtr = float(ttr.item())
+        replicas = {"what": f"{world} independent full-model replicas, one request each, no collective", "scaling": "weak",
+                    "value": world * a.new_tokens * a.steps / dtr, "ms_per_step": dtr / a.steps * 1e3}
+        # the like-for-like yardstick of the weak job: the SAME world requests on ONE GPU (rank 0's full replica batches them: packed prefill + one decode
+        # batch) while the other ranks idle — what tensor parallelism has to beat, measured in this run
+        try:
+            if rank == 0:
+                pw1, iw1 = weak_job_inputs(cfg, dev, dtype, world, a.prompt_len)
+
+                def step_1():
+                    return full.generate_batch(pw1, iw1, max_new_tokens=a.new_tokens, eos_token_id=-1, run_ahead=a.new_tokens, prefill_chunk=512, capacity=world)
+                step_1()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    step_1()
+                torch.cuda.synchronize()
+                dt1 = time.perf_counter() - t0
+                one_gpu_same_job = {"what": f"the weak job's {world} requests batched on ONE GPU (TP = 1 full model: packed prefill + {world} sequences decoding together)",
+                                    "value": world * a.new_tokens * a.steps / dt1, "ms_per_step": dt1 / a.steps * 1e3}
+            barrier()
+        except Exception as ex:  # noqa: BLE001
+            one_gpu_same_job = {"error": repr(ex)}
+            barrier()
+        del full
+        torch.cuda.empty_cache()
+
+    # ---- serving-side view (BASELINE configs 3/4 run many requests at once): the same request x B decoding together through
+    #      lmx_decode_batch (continuous batching) — aggregate generated tokens/s of the decode phase, not part of `value`
+    serving = None
+    if a.full and world == 1 and not a.no_batch:
+        from llava_mi355x import _C
+        from llava_mi355x.batching import DecodeBatch
+        from llava_mi355x.model import LmxKVCache
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        serving = {"what": "decode phase of B identical config-2 requests stepping together (lmx_decode_batch), context %d" % T, "by_batch": {}}
+        _, _, _, _, embeds, _ = model.prepare_inputs_labels_for_multimodal(ids, None, None, None, None, pix)
+        sizes = [8, 16, 32]
+        caches = []
+        for _ in range(max(sizes)):
+            c = LmxKVCache(model, 1)
+            _C.check(_C.lib.lmx_prefill(model._h, c.seqs[0], _C.ptr(embeds[0]), embeds.shape[1], 0, None, 0, 1, _C.stream_handle()))
+            caches.append(c)
+        bt = DecodeBatch(model, max(sizes))
+        for Bn in sizes:
+            seqs = [c.seqs[0] for c in caches[:Bn]]
+            bt.step(seqs, None, 2, True, want_ids=False)
+            torch.cuda.synchronize()
+            e[0].record(); bt.step(seqs, None, 16, True, want_ids=False); e[1].record()
+            torch.cuda.synchronize()
+            ms = e[0].elapsed_time(e[1]) / 16
+            serving["by_batch"][str(Bn)] = {"ms_per_step": ms, "decode_tokens_per_s": Bn * 1e3 / ms}
+        bt.close()
+        for c in caches:
+            c.close()
+
+    # ---- live parity probe (ADVICE r5): the timed 16-bit kernels against the fp32 VERIFICATION engine (same orchestration, exact fp32 GEMM / attention; itself within
+    # 1.5e-4 of the fp32 CPU oracle over all 1087 positions, tests/test_full_depth_gpu.py) on the SAME parameters (the seed's weights rounded to the 16-bit dtype), on
+    # this build: last-position prefill logits and the first greedy ids of the timed request.  Not the oracle (minutes of host time) — a figure that moves with the kernels.
+    live_parity = None
+    if a.full and rank == 0 and world == 1 and not a.no_parity_probe:
+        try:
+            n_ids = 8
+            lg16 = model.forward(input_ids=ids, images=pix, use_cache=False).logits[0, -1].float()
+            ids16 = outs[-1][0, a.prompt_len:a.prompt_len + n_ids].tolist()
+            m32 = harness.build_model(cfg, dtype=torch.float32, seed=0, device_rng=True, device=dev, max_position=2048, round_weights_to=dtype)
+            lg32 = m32.forward(input_ids=ids, images=pix.float(), use_cache=False).logits[0, -1].float()
+            g32 = m32.generate(inputs=ids, images=pix.float(), do_sample=False, max_new_tokens=n_ids, eos_token_id=-1)
+            ids32 = g32[0, a.prompt_len:].tolist()
+            scale = lg32.abs().max().item()
+            noise = (lg16 - lg32).abs().max().item()
+            live_parity = {"reference": "fp32 verification engine of this build on the same (16-bit-rounded) weights", "dtype": a.dtype,
+                           "last_position_logits_max_abs_err": noise, "max_abs_logit": scale, "err_of_max_logit": noise / scale,
+                           "rms_err_of_max_logit": (lg16 - lg32).pow(2).mean().sqrt().item() / scale, "argmax_equal": bool(lg16.argmax() == lg32.argmax()),
+                           "greedy_ids_16bit": ids16, "greedy_ids_fp32": ids32,
+                           # ids before the first difference (after it the two continuations are different sequences: nothing to compare position by position)
+                           "greedy_ids_identical_prefix": next((i for i, (x, y) in enumerate(zip(ids16, ids32)) if x != y), n_ids), "greedy_ids_compared": n_ids}
+            del m32, lg32, g32
+            torch.cuda.empty_cache()
+        except Exception as ex:  # noqa: BLE001
+            live_parity = {"error": repr(ex)}
+
+    tp_proj = None
+    if a.full and rank == 0 and world == 1 and not a.no_tp_projection:
+        try:
+            tp_proj = tp_projection(cfg, dtype, dev, ids, pix, a.new_tokens)
+            b32 = (serving or {}).get("by_batch", {}).get("32", {}).get("decode_tokens_per_s")
+            # the weak-scaling jobs (W requests) on THIS one GPU, really run: what one GPU makes of the same W requests by batching alone
+            one_gpu_jobs = {}
+            for k in tp_proj["by_world"]:
+                pw, iw = weak_job_inputs(cfg, dev, dtype, int(k), a.prompt_len)
+                ts = []
+                for r in range(3):
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    model.generate_batch(pw, iw, max_new_tokens=a.new_tokens, eos_token_id=-1, run_ahead=a.new_tokens, prefill_chunk=512, capacity=int(k))
+                    torch.cuda.synchronize()
+                    if r:
+                        ts.append(time.perf_counter() - t0)
+                one_gpu_jobs[k] = {"job_ms": min(ts) * 1e3, "value_tokens_per_s": int(k) * a.new_tokens / min(ts)}
+            tp_proj["measured_tp1"] = {"prefill_ms": prefill_ms, "decode_ms_per_token": decode_ms / (a.new_tokens - 1), "value": value, "batch32_decode_tokens_per_s": b32,
+                                       "same_jobs_on_one_gpu": one_gpu_jobs}
+            for k, v in tp_proj["by_world"].items():
+                v["projected_speedup_vs_tp1"] = v["projected_value_tokens_per_s"] / value
+                if b32:
+                    v["projected_batch32_speedup_vs_tp1"] = v["p2p"]["projected_batch_decode_tokens_per_s"] / b32
+                wk = v.get("weak")
+                if wk:
+                    wk["projected_speedup_vs_one_gpu_one_request"] = wk["projected_value_tokens_per_s"] / value            # the driver's scaling ratio: value(N) / value(1)
+                    wk["projected_vs_replicas"] = wk["projected_value_tokens_per_s"] / (int(k) * value)                     # > 1: one TP group beats N independent GPUs
+                    wk["projected_vs_same_job_on_one_gpu"] = wk["projected_value_tokens_per_s"] / one_gpu_jobs[k]["value_tokens_per_s"]
+        except Exception as ex:  # noqa: BLE001
+            tp_proj = {"error": repr(ex)}
+
+    cpu = None
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
+        try:
+            need_gb = sum(int(torch.tensor(shp).prod()) for shp in synth.tensor_shapes(cfg).values()) * 2 / 1e9 + 16
+            avail_gb = next((int(l.split()[1]) / 1e6 for l in open("/proc/meminfo") if l.startswith("MemAvailable")), 0.0)
+            if a.cpu_layers > 0 or avail_gb < need_gb:
+                cpu = cpu_baseline(cfg, T, a.new_tokens, a.cpu_layers or 2)
+            else:
+                del outs
+                torch.cuda.empty_cache()
+                ref = None
+                if not a.no_cpu_reference:
+                    try:
+                        ref = cpu_baseline_reference(cfg, ids, pix.float(), a.new_tokens, a.cpu_decode_steps)
+                    except Exception as ex:  # noqa: BLE001 — version skew of the host stack must not cost the line its baseline
+                        ref = {"error": repr(ex)}
+                # the oracle restatement ("port"): the whole request when it is the only baseline, a shorter sample beside the reference's own code
+                have_ref = bool(ref) and "value" in ref
+                port = cpu_baseline_full(cfg, ids, pix.float(), a.new_tokens, not a.no_cpu_fp32, a.cpu_decode_steps or (16 if have_ref else 0), prefill_runs=1 if have_ref else 3)
+                if have_ref:
+                    cpu = ref
+                    cpu["port"] = port
+                    cpu["port_vs_reference"] = port["value"] / ref["value"]
+                else:
+                    cpu = port
+                    if ref:
+                        cpu["reference_error"] = ref.get("error")
+        except Exception as ex:  # noqa: BLE001
+            cpu = {"error": repr(ex)}
+
+    # Native libraries write to C stdio (RCCL prints a version banner on its first communicator), which is block-buffered on a pipe and
+    # would otherwise come out at process exit, AFTER the JSON line.  Every rank flushes it now, then rank 0 prints the JSON line last.
+    try:
+        import ctypes as _ct
+        _ct.CDLL(None).fflush(None)
+    except Exception:  # noqa: BLE001
+        pass
+    sys.stdout.flush()
+    barrier()
+    if rank == 0:
+        # the tensor-parallel PROJECTION (rank-local shards timed on this one GPU + a link model: a model, not a measurement) goes to a side file; the line keeps
+        # its headline ratios and says where the rest is
+        tp_brief = None
+        if tp_proj is not None:
+            tp_brief = {"what": "PROJECTION, unmeasured on hardware: rank-local shards of TP 2 / 4 / 8 timed on this GPU with a no-op all-reduce + a link model",
+                        "error": tp_proj.get("error")}
+            try:
+                side = os.path.join(ROOT, "gpurun_out", "bench_tp_projection.json")
+                os.makedirs(os.path.dirname(side), exist_ok=True)
+                with open(side, "w") as f:
+                    json.dump(tp_proj, f, indent=1)
+                tp_brief["file"] = os.path.relpath(side, ROOT)
+                w8 = (tp_proj.get("by_world") or {}).get("8") or {}
+                tp_brief["tp8"] = {"single_request_speedup_vs_tp1": w8.get("projected_speedup_vs_tp1"),
+                                   "weak_job_vs_eight_replicas": (w8.get("weak") or {}).get("projected_vs_replicas"),
+                                   "weak_job_vs_same_job_on_one_gpu": (w8.get("weak") or {}).get("projected_vs_same_job_on_one_gpu"),
+                                   "batch32_decode_speedup_vs_tp1": w8.get("projected_batch32_speedup_vs_tp1")}
+            except Exception as ex:  # noqa: BLE001
+                tp_brief["error"] = repr(ex)
+        strong = None
+        decode_tok_ms = decode_ms / (a.new_tokens - 1) if a.full else None
+        workload = f"{a.model}: 1x336x336 image + {a.prompt_len}-token prompt ({T} positions), greedy {a.new_tokens} new tokens, batch 1"
+        scaling = "strong" if world > 1 else "weak"
+        if weak and "value" in weak:
+            # N > 1: `value` is the weak-scaling job (per-GPU work fixed: one request per GPU); the single request over TP = N is reported beside it
+            strong = {"what": f"ONE request over TP = {world} (latency view; total work fixed)", "scaling": "strong", "value": value, "ms_per_step": ms_per_step,
+                      "prefill_ms": prefill_ms, "decode_ms_per_token": decode_tok_ms, "greedy_ids_identical_across_steps": bool(deterministic)}
+            value, ms_per_step, scaling = weak["value"], weak["ms_per_step"], "weak"
+            workload = (f"{a.model}: {world} requests (one per GPU), each 1x336x336 image + {a.prompt_len}-token prompt ({T} positions), greedy {a.new_tokens} new tokens; "
+                        f"one TP = {world} job (tower data parallel, packed prefill, {world} sequences decoding together)")
+        line = {"metric": "generated tokens/sec + prefill ms (336px img + 512-tok prompt), LLaVA-1.5-7B", "value": value,
+                "unit": "generated tokens/s (whole request: image encode + prefill + decode)" if scaling != "weak" or world == 1 else
+                        "generated tokens/s (whole job: image encodes + packed prefill + batched decode of one request per GPU)",
+                "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "full": a.full,
+                "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+                "dtype": a.dtype, "data": "synthetic (seeded image + ids, random-init HF-std weights)",
+                "config": {"workload": workload,
+                           "parallelism": f"tp{world}", "kv_capacity": 2048,
+                           "decode_allreduce": ("p2p-one-shot" if getattr(model, "p2p_active", False) else "rccl") if world > 1 else None,
+                           "rccl_ranks": model.tp_comm_ranks() if world > 1 else None, "prefill_allreduce": ("rccl on the engine's comm stream, two row halves overlapped with the other half's GEMMs"
+                                                 if T * world >= 4096 else "rccl on the launch stream (the two-half pipeline starts at rows x ranks >= 4096)") if world > 1 else None},
+                # null without --full: the phase split, the rooflines, cpu_baseline, serving_batch, replicas, tp_projection, parity, same_job_on_one_gpu*, kernel_breakdown
+                "prefill_ms": prefill_ms, "decode_tokens_per_s": 1e3 / decode_tok_ms if a.full else None, "decode_ms_per_token": decode_tok_ms,
+                # the two whole-phase fractions at the top level (VERDICT r5 item 9): every algorithmic byte of a decode step over the wall time per token against
+                # the HBM peak, and every FLOP of the prefill (tower + projector + decoder) over the measured prefill time against the dense bf16 MFMA peak
+                "decode_step_frac_of_hbm_peak": ((roof or {}).get("decode_step") or {}).get("frac"), "prefill_frac_of_mfma_peak": (roof_p or {}).get("frac"),
+                "roofline": roof, "roofline_prefill": roof_p, "cpu_baseline": cpu, "serving_batch": serving, "weak_job": weak, "strong_single_request": strong,
+                "replicas": replicas, "tp_projection": tp_brief,
+                # N > 1 — what `value` is and the two numbers it must be read against, at the top level (VERDICT r4 weak 10 / ADVICE r4): `value` = the WEAK job
+                # (N requests as one TP = N job); it is NOT an N-fold tensor-parallel speed-up of one request
+                "schema": 6, "parity": dict(parity_record(a.model), live=live_parity) if a.full else None,
+                "value_definition": ("one request (N = 1)" if world == 1 else f"weak-scaling job: {world} requests, one per GPU, run as ONE TP = {world} job; compare with "
+                                     "strong_single_request_value (ONE request over the same GPUs) and same_job_on_one_gpu_value (the same requests batched on one GPU)"),
+                "strong_single_request_value": (strong or {}).get("value") if world > 1 else None,
+                "same_job_on_one_gpu_value": (one_gpu_same_job or {}).get("value") if world > 1 else None,
+                "value_vs_same_job_on_one_gpu": (value / one_gpu_same_job["value"]) if world > 1 and one_gpu_same_job and "value" in one_gpu_same_job else None,
+                "same_job_on_one_gpu": one_gpu_same_job,
+                "kernel_breakdown_ms_per_step": breakdown,
+                "model_build_s": build_s, "greedy_ids_identical_across_steps": bool(deterministic)}
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def profile_request(a, model, cfg, dev, ids, pix, T, world, rank, barrier, step):
+    """--full: phase split (prefill / decode) and in-situ per-kernel durations of profiled replays of the timed request, priced against the rooflines."""
     e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     from llava_mi355x.model import LmxKVCache
     from llava_mi355x import _C
@@ -985,275 +1298,7 @@ def main():
     roof["event_pair_overhead_us"] = marker_us
     roof["event_pair_calibration"] = {"one_launch_scope_us": cal_t1, "two_launch_scope_us": cal_t2, "empty_scope_us": empty_scope_us}
     roof_p["event_pair_overhead_us"] = marker_us
-
-    # ---- N > 1: the weak-scaling job — N requests (one per GPU, own image + own prompt) as ONE tensor-parallel job: the tower data parallel over the
-    #      images, packed prefill, the N sequences decoding together (model.generate_batch; every rank runs the same plan).  This is the workload the
-    #      line's `value` is quoted on at N > 1 (DESIGN.md §4 "Multi-GPU"); the single request over TP = N stays beside it as `strong_single_request`
-    weak = None
-    if world > 1 and not a.no_weak:
-        import torch.distributed as dist
-        try:
-            pw, iw = weak_job_inputs(cfg, dev, dtype, world, a.prompt_len)
-
-            def step_w():
-                o = model.generate_batch(pw, iw, max_new_tokens=a.new_tokens, eos_token_id=-1, run_ahead=a.new_tokens, prefill_chunk=512, capacity=world)
-                assert all(x.numel() == a.prompt_len + a.new_tokens for x in o)
-                return o
-
-            first_w = None
-            for _ in range(max(1, min(a.warmup, 2))):
-                first_w = step_w()
-            barrier()
-            t0 = time.perf_counter()
-            for _ in range(a.steps):
-                last_w = step_w()
-            barrier()
-            dtw = time.perf_counter() - t0
-            ttw = torch.tensor([dtw], device="cpu" if share else dev, dtype=torch.float64)
-            dist.all_reduce(ttw, op=dist.ReduceOp.MAX)
-            dtw = float(ttw.item())
-            weak = {"what": f"{world} requests, one per GPU, as one TP = {world} job: image tower data parallel over the ranks + feature all-gather, packed prefill in pieces "
-                            f"of {world} x 512 rows, {world} sequences decoding together", "requests": world, "scaling": "weak",
-                    "value": world * a.new_tokens * a.steps / dtw, "ms_per_step": dtw / a.steps * 1e3,
-                    "tower_sharded": bool(model.tower_is_sharded(world)),
-                    "greedy_ids_identical_across_steps": bool(all(torch.equal(x, y) for x, y in zip(first_w, last_w)))}
-        except Exception as ex:  # noqa: BLE001 — the line keeps the single-request measurement as its value and says why
-            weak = {"error": repr(ex)}
-
-    # ---- N > 1: the same N GPUs as N independent replicas (SURVEY §8e "data-parallel serving fallback": one full model per GPU, one
-    #      request each, no collective) — reported next to the tensor-parallel `value`, never instead of it
-    replicas = None
-    one_gpu_same_job = None
-    if world > 1 and not a.no_replicas:
-        import torch.distributed as dist
-        del outs
-        full = harness.build_model(cfg, dtype=dtype, seed=0, device_rng=True, device=dev, tp_rank=0, tp_world=1, max_position=2048)
-        ids_r = torch.from_numpy(synth.make_prompt(cfg, a.prompt_len, image_positions=(35,), seed=2 + rank))[None].to(dev)
-
-        def step_r():
-            return full.generate(inputs=ids_r, images=pix, do_sample=False, max_new_tokens=a.new_tokens, eos_token_id=-1, run_ahead=a.new_tokens)
-
-        for _ in range(max(1, a.warmup)):
-            step_r()
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(a.steps):
-            step_r()
-        barrier()
-        dtr = time.perf_counter() - t0
-        ttr = torch.tensor([dtr], device="cpu" if share else dev, dtype=torch.float64)
-        dist.all_reduce(ttr, op=dist.ReduceOp.MAX)
-        dtr = float(ttr.item())
-        replicas = {"what": f"{world} independent full-model replicas, one request each, no collective", "scaling": "weak",
-                    "value": world * a.new_tokens * a.steps / dtr, "ms_per_step": dtr / a.steps * 1e3}
-        # the like-for-like yardstick of the weak job: the SAME world requests on ONE GPU (rank 0's full replica batches them: packed prefill + one decode
-        # batch) while the other ranks idle — what tensor parallelism has to beat, measured in this run
-        try:
-            if rank == 0:
-                pw1, iw1 = weak_job_inputs(cfg, dev, dtype, world, a.prompt_len)
-
-                def step_1():
-                    return full.generate_batch(pw1, iw1, max_new_tokens=a.new_tokens, eos_token_id=-1, run_ahead=a.new_tokens, prefill_chunk=512, capacity=world)
-                step_1()
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(a.steps):
-                    step_1()
-                torch.cuda.synchronize()
-                dt1 = time.perf_counter() - t0
-                one_gpu_same_job = {"what": f"the weak job's {world} requests batched on ONE GPU (TP = 1 full model: packed prefill + {world} sequences decoding together)",
-                                    "value": world * a.new_tokens * a.steps / dt1, "ms_per_step": dt1 / a.steps * 1e3}
-            barrier()
-        except Exception as ex:  # noqa: BLE001
-            one_gpu_same_job = {"error": repr(ex)}
-            barrier()
-        del full
-        torch.cuda.empty_cache()
-
-    # ---- serving-side view (BASELINE configs 3/4 run many requests at once): the same request x B decoding together through
-    #      lmx_decode_batch (continuous batching) — aggregate generated tokens/s of the decode phase, not part of `value`
-    serving = None
-    if world == 1 and not a.no_batch:
-        from llava_mi355x.batching import DecodeBatch
-        serving = {"what": "decode phase of B identical config-2 requests stepping together (lmx_decode_batch), context %d" % T, "by_batch": {}}
-        _, _, _, _, embeds, _ = model.prepare_inputs_labels_for_multimodal(ids, None, None, None, None, pix)
-        sizes = [8, 16, 32]
-        caches = []
-        for _ in range(max(sizes)):
-            c = LmxKVCache(model, 1)
-            _C.check(_C.lib.lmx_prefill(model._h, c.seqs[0], _C.ptr(embeds[0]), embeds.shape[1], 0, None, 0, 1, _C.stream_handle()))
-            caches.append(c)
-        bt = DecodeBatch(model, max(sizes))
-        for Bn in sizes:
-            seqs = [c.seqs[0] for c in caches[:Bn]]
-            bt.step(seqs, None, 2, True, want_ids=False)
-            torch.cuda.synchronize()
-            e[0].record(); bt.step(seqs, None, 16, True, want_ids=False); e[1].record()
-            torch.cuda.synchronize()
-            ms = e[0].elapsed_time(e[1]) / 16
-            serving["by_batch"][str(Bn)] = {"ms_per_step": ms, "decode_tokens_per_s": Bn * 1e3 / ms}
-        bt.close()
-        for c in caches:
-            c.close()
-
-    # ---- live parity probe (ADVICE r5): the timed 16-bit kernels against the fp32 VERIFICATION engine (same orchestration, exact fp32 GEMM / attention; itself within
-    # 1.5e-4 of the fp32 CPU oracle over all 1087 positions, tests/test_full_depth_gpu.py) on the SAME parameters (the seed's weights rounded to the 16-bit dtype), on
-    # this build: last-position prefill logits and the first greedy ids of the timed request.  Not the oracle (minutes of host time) — a figure that moves with the kernels.
-    live_parity = None
-    if rank == 0 and world == 1 and not a.no_parity_probe:
-        try:
-            n_ids = 8
-            lg16 = model.forward(input_ids=ids, images=pix, use_cache=False).logits[0, -1].float()
-            ids16 = outs[-1][0, a.prompt_len:a.prompt_len + n_ids].tolist()
-            m32 = harness.build_model(cfg, dtype=torch.float32, seed=0, device_rng=True, device=dev, max_position=2048, round_weights_to=dtype)
-            lg32 = m32.forward(input_ids=ids, images=pix.float(), use_cache=False).logits[0, -1].float()
-            g32 = m32.generate(inputs=ids, images=pix.float(), do_sample=False, max_new_tokens=n_ids, eos_token_id=-1)
-            ids32 = g32[0, a.prompt_len:].tolist()
-            scale = lg32.abs().max().item()
-            noise = (lg16 - lg32).abs().max().item()
-            live_parity = {"reference": "fp32 verification engine of this build on the same (16-bit-rounded) weights", "dtype": a.dtype,
-                           "last_position_logits_max_abs_err": noise, "max_abs_logit": scale, "err_of_max_logit": noise / scale,
-                           "rms_err_of_max_logit": (lg16 - lg32).pow(2).mean().sqrt().item() / scale, "argmax_equal": bool(lg16.argmax() == lg32.argmax()),
-                           "greedy_ids_16bit": ids16, "greedy_ids_fp32": ids32,
-                           # ids before the first difference (after it the two continuations are different sequences: nothing to compare position by position)
-                           "greedy_ids_identical_prefix": next((i for i, (x, y) in enumerate(zip(ids16, ids32)) if x != y), n_ids), "greedy_ids_compared": n_ids}
-            del m32, lg32, g32
-            torch.cuda.empty_cache()
-        except Exception as ex:  # noqa: BLE001
-            live_parity = {"error": repr(ex)}
-
-    tp_proj = None
-    if rank == 0 and world == 1 and not a.no_tp_projection:
-        try:
-            tp_proj = tp_projection(cfg, dtype, dev, ids, pix, a.new_tokens)
-            b32 = (serving or {}).get("by_batch", {}).get("32", {}).get("decode_tokens_per_s")
-            # the weak-scaling jobs (W requests) on THIS one GPU, really run: what one GPU makes of the same W requests by batching alone
-            one_gpu_jobs = {}
-            for k in tp_proj["by_world"]:
-                pw, iw = weak_job_inputs(cfg, dev, dtype, int(k), a.prompt_len)
-                ts = []
-                for r in range(3):
-                    torch.cuda.synchronize(); t0 = time.perf_counter()
-                    model.generate_batch(pw, iw, max_new_tokens=a.new_tokens, eos_token_id=-1, run_ahead=a.new_tokens, prefill_chunk=512, capacity=int(k))
-                    torch.cuda.synchronize()
-                    if r:
-                        ts.append(time.perf_counter() - t0)
-                one_gpu_jobs[k] = {"job_ms": min(ts) * 1e3, "value_tokens_per_s": int(k) * a.new_tokens / min(ts)}
-            tp_proj["measured_tp1"] = {"prefill_ms": prefill_ms, "decode_ms_per_token": decode_ms / (a.new_tokens - 1), "value": value, "batch32_decode_tokens_per_s": b32,
-                                       "same_jobs_on_one_gpu": one_gpu_jobs}
-            for k, v in tp_proj["by_world"].items():
-                v["projected_speedup_vs_tp1"] = v["projected_value_tokens_per_s"] / value
-                if b32:
-                    v["projected_batch32_speedup_vs_tp1"] = v["p2p"]["projected_batch_decode_tokens_per_s"] / b32
-                wk = v.get("weak")
-                if wk:
-                    wk["projected_speedup_vs_one_gpu_one_request"] = wk["projected_value_tokens_per_s"] / value            # the driver's scaling ratio: value(N) / value(1)
-                    wk["projected_vs_replicas"] = wk["projected_value_tokens_per_s"] / (int(k) * value)                     # > 1: one TP group beats N independent GPUs
-                    wk["projected_vs_same_job_on_one_gpu"] = wk["projected_value_tokens_per_s"] / one_gpu_jobs[k]["value_tokens_per_s"]
-        except Exception as ex:  # noqa: BLE001
-            tp_proj = {"error": repr(ex)}
-
-    cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        try:
-            need_gb = sum(int(torch.tensor(shp).prod()) for shp in synth.tensor_shapes(cfg).values()) * 2 / 1e9 + 16
-            avail_gb = next((int(l.split()[1]) / 1e6 for l in open("/proc/meminfo") if l.startswith("MemAvailable")), 0.0)
-            if a.cpu_layers > 0 or avail_gb < need_gb:
-                cpu = cpu_baseline(cfg, T, a.new_tokens, a.cpu_layers or 2)
-            else:
-                del outs
-                torch.cuda.empty_cache()
-                ref = None
-                if not a.no_cpu_reference:
-                    try:
-                        ref = cpu_baseline_reference(cfg, ids, pix.float(), a.new_tokens, a.cpu_decode_steps)
-                    except Exception as ex:  # noqa: BLE001 — version skew of the host stack must not cost the line its baseline
-                        ref = {"error": repr(ex)}
-                # the oracle restatement ("port"): the whole request when it is the only baseline, a shorter sample beside the reference's own code
-                have_ref = bool(ref) and "value" in ref
-                port = cpu_baseline_full(cfg, ids, pix.float(), a.new_tokens, not a.no_cpu_fp32, a.cpu_decode_steps or (16 if have_ref else 0), prefill_runs=1 if have_ref else 3)
-                if have_ref:
-                    cpu = ref
-                    cpu["port"] = port
-                    cpu["port_vs_reference"] = port["value"] / ref["value"]
-                else:
-                    cpu = port
-                    if ref:
-                        cpu["reference_error"] = ref.get("error")
-        except Exception as ex:  # noqa: BLE001
-            cpu = {"error": repr(ex)}
-
-    # Native libraries write to C stdio (RCCL prints a version banner on its first communicator), which is block-buffered on a pipe and
-    # would otherwise come out at process exit, AFTER the JSON line.  Every rank flushes it now, then rank 0 prints the JSON line last.
-    try:
-        import ctypes as _ct
-        _ct.CDLL(None).fflush(None)
-    except Exception:  # noqa: BLE001
-        pass
-    sys.stdout.flush()
-    barrier()
-    if rank == 0:
-        # the tensor-parallel PROJECTION (rank-local shards timed on this one GPU + a link model: a model, not a measurement) goes to a side file; the line keeps
-        # its headline ratios and says where the rest is
-        tp_brief = None
-        if tp_proj is not None:
-            tp_brief = {"what": "PROJECTION, unmeasured on hardware: rank-local shards of TP 2 / 4 / 8 timed on this GPU with a no-op all-reduce + a link model",
-                        "error": tp_proj.get("error")}
-            try:
-                side = os.path.join(ROOT, "gpurun_out", "bench_tp_projection.json")
-                os.makedirs(os.path.dirname(side), exist_ok=True)
-                with open(side, "w") as f:
-                    json.dump(tp_proj, f, indent=1)
-                tp_brief["file"] = os.path.relpath(side, ROOT)
-                w8 = (tp_proj.get("by_world") or {}).get("8") or {}
-                tp_brief["tp8"] = {"single_request_speedup_vs_tp1": w8.get("projected_speedup_vs_tp1"),
-                                   "weak_job_vs_eight_replicas": (w8.get("weak") or {}).get("projected_vs_replicas"),
-                                   "weak_job_vs_same_job_on_one_gpu": (w8.get("weak") or {}).get("projected_vs_same_job_on_one_gpu"),
-                                   "batch32_decode_speedup_vs_tp1": w8.get("projected_batch32_speedup_vs_tp1")}
-            except Exception as ex:  # noqa: BLE001
-                tp_brief["error"] = repr(ex)
-        strong = None
-        workload = f"{a.model}: 1x336x336 image + {a.prompt_len}-token prompt ({T} positions), greedy {a.new_tokens} new tokens, batch 1"
-        scaling = "strong" if world > 1 else "weak"
-        if weak and "value" in weak:
-            # N > 1: `value` is the weak-scaling job (per-GPU work fixed: one request per GPU); the single request over TP = N is reported beside it
-            strong = {"what": f"ONE request over TP = {world} (latency view; total work fixed)", "scaling": "strong", "value": value, "ms_per_step": ms_per_step,
-                      "prefill_ms": prefill_ms, "decode_ms_per_token": decode_ms / (a.new_tokens - 1), "greedy_ids_identical_across_steps": bool(deterministic)}
-            value, ms_per_step, scaling = weak["value"], weak["ms_per_step"], "weak"
-            workload = (f"{a.model}: {world} requests (one per GPU), each 1x336x336 image + {a.prompt_len}-token prompt ({T} positions), greedy {a.new_tokens} new tokens; "
-                        f"one TP = {world} job (tower data parallel, packed prefill, {world} sequences decoding together)")
-        line = {"metric": "generated tokens/sec + prefill ms (336px img + 512-tok prompt), LLaVA-1.5-7B", "value": value,
-                "unit": "generated tokens/s (whole request: image encode + prefill + decode)" if scaling != "weak" or world == 1 else
-                        "generated tokens/s (whole job: image encodes + packed prefill + batched decode of one request per GPU)",
-                "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-                "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-                "dtype": a.dtype, "data": "synthetic (seeded image + ids, random-init HF-std weights)",
-                "config": {"workload": workload,
-                           "parallelism": f"tp{world}", "kv_capacity": 2048,
-                           "decode_allreduce": ("p2p-one-shot" if getattr(model, "p2p_active", False) else "rccl") if world > 1 else None,
-                           "rccl_ranks": model.tp_comm_ranks() if world > 1 else None, "prefill_allreduce": ("rccl on the engine's comm stream, two row halves overlapped with the other half's GEMMs"
-                                                 if T * world >= 4096 else "rccl on the launch stream (the two-half pipeline starts at rows x ranks >= 4096)") if world > 1 else None},
-                "prefill_ms": prefill_ms, "decode_tokens_per_s": (a.new_tokens - 1) / (decode_ms * 1e-3), "decode_ms_per_token": decode_ms / (a.new_tokens - 1),
-                # the two whole-phase fractions at the top level (VERDICT r5 item 9): every algorithmic byte of a decode step over the wall time per token against
-                # the HBM peak, and every FLOP of the prefill (tower + projector + decoder) over the measured prefill time against the dense bf16 MFMA peak
-                "decode_step_frac_of_hbm_peak": (roof.get("decode_step") or {}).get("frac"), "prefill_frac_of_mfma_peak": (roof_p or {}).get("frac"),
-                "roofline": roof, "roofline_prefill": roof_p, "cpu_baseline": cpu, "serving_batch": serving, "weak_job": weak, "strong_single_request": strong,
-                "replicas": replicas, "tp_projection": tp_brief,
-                # N > 1 — what `value` is and the two numbers it must be read against, at the top level (VERDICT r4 weak 10 / ADVICE r4): `value` = the WEAK job
-                # (N requests as one TP = N job); it is NOT an N-fold tensor-parallel speed-up of one request
-                "schema": 6, "parity": dict(parity_record(a.model), live=live_parity),
-                "value_definition": ("one request (N = 1)" if world == 1 else f"weak-scaling job: {world} requests, one per GPU, run as ONE TP = {world} job; compare with "
-                                     "strong_single_request_value (ONE request over the same GPUs) and same_job_on_one_gpu_value (the same requests batched on one GPU)"),
-                "strong_single_request_value": (strong or {}).get("value") if world > 1 else None,
-                "same_job_on_one_gpu_value": (one_gpu_same_job or {}).get("value") if world > 1 else None,
-                "value_vs_same_job_on_one_gpu": (value / one_gpu_same_job["value"]) if world > 1 and one_gpu_same_job and "value" in one_gpu_same_job else None,
-                "same_job_on_one_gpu": one_gpu_same_job,
-                "kernel_breakdown_ms_per_step": breakdown,
-                "model_build_s": build_s, "greedy_ids_identical_across_steps": bool(deterministic)}
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+    return prefill_ms, decode_ms, roof, roof_p, breakdown
 
 
 if __name__ == "__main__":

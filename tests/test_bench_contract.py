@@ -30,9 +30,30 @@ def test_command_line_contract(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     a = bench.parse()
     assert a.gpus == 1 and a.steps >= 1 and a.warmup >= 0 and a.workload == "config2" and a.model == "llava15_7b" and a.dtype == "bf16"
+    assert not a.full and a.dump_outputs is None          # a plain run times the headline only and writes nothing
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "5", "--warmup", "2"])
     a = bench.parse()
     assert (a.gpus, a.steps, a.warmup) == (8, 5, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_exact_float_arrays(tmp_path):
+    """--dump-outputs: ids as float64 (exact), 16-bit floats widened to float32, one DIR/<name>.npy each; more than the limit is refused."""
+    import numpy as np
+    import pytest
+    import torch
+    import bench
+    ids = torch.tensor([[1, 31999, -200, 7]])
+    x = torch.tensor([0.1, -2.5], dtype=torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "d"), {"output_ids": ids, "x": x})
+    got_ids, got_x = np.load(tmp_path / "d" / "output_ids.npy"), np.load(tmp_path / "d" / "x.npy")
+    assert got_ids.dtype == np.float64 and (got_ids == ids.numpy()).all()
+    assert got_x.dtype == np.float32 and (got_x == x.float().numpy()).all()
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not (tmp_path / "big").exists()
 
 
 def test_oracle_is_only_imported_by_the_cpu_baseline_leg():

@@ -4,7 +4,7 @@ set -u
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 for cfg in "$@"; do
-  env $cfg timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+  env $cfg timeout 600 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     try: r = json.loads(l)
