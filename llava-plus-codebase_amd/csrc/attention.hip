@@ -131,6 +131,7 @@ __global__ __launch_bounds__(512) void flash_prefill2_kernel(FlashArgs a) {
     };
 
     const int nrounds = (ntiles + 1) >> 1;
+    const int tail_round = ntiles * FA_KT > a.kv_len ? (ntiles - 1) >> 1 : -1;       // the round that holds a tile reaching past kv_len, if any
     // this wave's group stages tile 2 r + grp of round r into slot (r % NRND) * 2 + grp (nothing if that tile does not exist)
     auto stage_round = [&](int r) { const int t = 2 * r + grp; if (t < ntiles) stage(t, (r % NRND) * 2 + grp); };
 #pragma unroll
@@ -143,6 +144,31 @@ __global__ __launch_bounds__(512) void flash_prefill2_kernel(FlashArgs a) {
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();          // round r visible to every wave; everyone is done with round r - 1 (its slots are free)
         if (r + NRND - 1 < nrounds) stage_round(r + NRND - 1);
+        if (r == tail_round) {
+            // The last tile reaches past kv_len.  Its keys there get P = 0, but their Vᵀ bytes are whatever the cache holds (a pooled sequence's earlier
+            // request, a reused scratch pair): the group that owns the tile clears them in LDS, never 0 x NaN in Vᵀ · Pᵀ.  Workgroup-uniform, once per
+            // workgroup at most; full tiles run the loop as before.
+            if (t == ntiles - 1) {
+                char* vb_w = smem + ((r % NRND) * 2 + grp) * BUF_BYTES + K_BYTES;
+                const int nv = a.kv_len - t * FA_KT;                          // valid keys of the tile, 1 .. 63
+#pragma unroll
+                for (int i = 0; i < D * 8 / 256; ++i) {
+                    const int pc = wave * 64 + lane + 256 * i;                // (d row, 8-key chunk) pair of this lane
+                    const int row = pc >> 3, chunk = pc & 7;
+                    const int n = nv - chunk * 8;                             // valid keys of the chunk
+                    if (n < 8) {
+                        uint4* p = reinterpret_cast<uint4*>(vb_w + vt_lds_chunk(row, chunk));
+                        uint4 u = *p;
+                        u.x &= (n > 0 ? 0x0000ffffu : 0u) | (n > 1 ? 0xffff0000u : 0u);
+                        u.y &= (n > 2 ? 0x0000ffffu : 0u) | (n > 3 ? 0xffff0000u : 0u);
+                        u.z &= (n > 4 ? 0x0000ffffu : 0u) | (n > 5 ? 0xffff0000u : 0u);
+                        u.w &= (n > 6 ? 0x0000ffffu : 0u) | (n > 7 ? 0xffff0000u : 0u);
+                        *p = u;
+                    }
+                }
+            }
+            __syncthreads();
+        }
         if (t >= ntiles) continue;             // odd tile count: group 1 sits out the last round (it still takes the barriers)
         const char* kb_ = smem + ((r % NRND) * 2 + grp) * BUF_BYTES;
         const char* vb_ = kb_ + K_BYTES;
@@ -397,6 +423,10 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(DecodeAttnArgs a) {
             float acc = 0.f;
             for (int kb = 0; kb < nk_pad; kb += 64) {
                 float vv[8]; load8<T>(Vt + (size_t)d * a.s_max + k_begin + kb + sub * 8, vv);
+                if (kb + 64 > nk) {              // the line that holds the split's end: P is 0 past it and the Vᵀ values are cleared (never 0 x NaN)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) vv[e] = kb + sub * 8 + e < nk ? vv[e] : 0.f;
+                }
                 const float4 p0 = *reinterpret_cast<const float4*>(sc_lds + kb + sub * 8);
                 const float4 p1 = *reinterpret_cast<const float4*>(sc_lds + kb + sub * 8 + 4);
                 acc = fmaf(p0.x, vv[0], acc); acc = fmaf(p0.y, vv[1], acc);

@@ -123,7 +123,16 @@ __device__ __forceinline__ void decode_fused_body(DecodeFusedArgs a, const int h
         __syncthreads();
         const float p_new = has_new ? red[4] : 0.f;
 
-        // ---- o = P · V from the registers loaded above ---------------------------------------------------------------------
+        // ---- o = P · V from the registers loaded above; past the cached keys (the newest key's slot, read before its append, and the tail behind it) P is 0
+        //      and the Vᵀ values are cleared, never 0 x NaN: only the chunk that holds `pos` ---------------------------------------------------------
+        if (nk_cached < DF_CHUNK) {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int db = 0; db < DB; ++db)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) vv[kb][db][e] = kb * 64 + s8 * 8 + e < nk_cached ? vv[kb][db][e] : 0.f;
+        }
         float acc[DB];
 #pragma unroll
         for (int db = 0; db < DB; ++db) acc[db] = 0.f;

@@ -195,7 +195,7 @@ int lmx_seq_create(lmx_model* m, lmx_seq** out) {
     }
     if (s) {
         // recycled sequence: wait for the last work that touched it (event recorded when it was released), then start clean.
-        // Stale K / V rows stay (finite values; every kernel masks by length), only the state words are cleared.
+        // Stale K / V rows stay (any values, NaN / Inf included: every kernel masks by length, tests/test_attn_cache_tails_gpu.py), only the state words are cleared.
         if (s->impl.ev_idle) LMX_CHECK_HIP(hipEventSynchronize(s->impl.ev_idle));
         s->impl.len = 0;
         s->impl.samp = SampleParams{};

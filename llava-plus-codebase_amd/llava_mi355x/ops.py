@@ -157,10 +157,27 @@ def decode_attn_step(qkv, kcache, vtcache, cos_sin, pos, n_heads, n_kv_heads, he
     return out
 
 
-def decode_attn_batch(qkv, kcaches, vtcaches, pos_words, cos_sin, n_heads, n_kv_heads, head_dim, n_split=None):
+def decode_fused(qkv, kcache, vtcache, cos_sin, pos, n_heads, n_kv_heads, head_dim, scratch=None):
+    """The decode step's attention launch of fp32 models (decode_fused_kernel, one sequence): RoPE(q, k_new) at `pos` (an int, or the int32 [1] device position
+    word the engine keeps), K / V^T append, attention over keys 0..pos in 128-key chunks merged by the last chunk to arrive.  qkv: one [q|k|v] row (pre-RoPE).
+    Returns the [n_heads * head_dim] output row."""
+    if not isinstance(pos, torch.Tensor):
+        pos = torch.tensor([int(pos)], dtype=torch.int32, device=qkv.device)
+    _need_cuda(qkv, kcache, vtcache, cos_sin, pos)
+    assert pos.dtype == torch.int32 and pos.numel() == 1
+    s_max = kcache.shape[1]
+    n_split = (s_max + 127) // 128
+    ws, cnt, out = scratch if scratch is not None else decode_attn_scratch(n_heads, n_split, head_dim, qkv.dtype, qkv.device)
+    check(lib.lmx_op_decode_fused(torch_dtype_code(qkv.dtype), head_dim, ptr(qkv), ptr(kcache), ptr(vtcache), ptr(cos_sin), ptr(pos), n_heads, n_kv_heads,
+                                  s_max, 1.0 / (head_dim ** 0.5), ptr(ws), ptr(cnt), ptr(out), 0, stream_handle()), "decode_fused")
+    return out
+
+
+def decode_attn_batch(qkv, kcaches, vtcaches, pos_words, cos_sin, n_heads, n_kv_heads, head_dim, n_split=None, out=None):
     """The decode BATCH's attention launch (continuous batching): row z of qkv [n_seq, (n_heads + 2 n_kv_heads) head_dim] (pre-RoPE) against sequence z's own
     caches kcaches[z] [n_kv_heads, s_max, D] / vtcaches[z] [n_kv_heads, D, s_max] and its device position word pos_words[z] (int32 [1]: keys already cached).
-    Appends the rotated key / the value at that position and returns the [n_seq, n_heads * head_dim] attention rows."""
+    Appends the rotated key / the value at that position and returns the [n_seq, n_heads * head_dim] attention rows (into `out` when given: rows may be a
+    column window of a wider buffer)."""
     import ctypes
     n_seq = qkv.shape[0]
     _need_cuda(qkv, cos_sin, *kcaches, *vtcaches, *pos_words)
@@ -172,7 +189,9 @@ def decode_attn_batch(qkv, kcaches, vtcaches, pos_words, cos_sin, n_heads, n_kv_
     ws = [torch.zeros(n_heads * n_split * (head_dim + 4), dtype=torch.float32, device=qkv.device) for _ in range(n_seq)]
     cnt = [torch.zeros(n_heads, dtype=torch.int32, device=qkv.device) for _ in range(n_seq)]
     tab = torch.empty(int(lib.lmx_op_decode_attn_batch_tab_bytes(n_seq)), dtype=torch.uint8, device=qkv.device)
-    out = torch.empty(n_seq, n_heads * head_dim, dtype=qkv.dtype, device=qkv.device)
+    if out is None:
+        out = torch.empty(n_seq, n_heads * head_dim, dtype=qkv.dtype, device=qkv.device)
+    assert out.shape == (n_seq, n_heads * head_dim) and out.stride(1) == 1
     check(lib.lmx_op_decode_attn_batch(torch_dtype_code(qkv.dtype), head_dim, ptr(qkv), qkv.stride(0), arr(kcaches), arr(vtcaches), arr(pos_words), arr(ws), arr(cnt),
                                        n_seq, ptr(cos_sin), n_heads, n_kv_heads, s_max, int(n_split), 1.0 / (head_dim ** 0.5), ptr(tab), ptr(out), out.stride(0),
                                        stream_handle()), "decode_attn_batch")

@@ -316,8 +316,8 @@ class TrainStep:
 
     def _kv_scratch(self, s_max: int, dtype, lane: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """K / V^T cache of one sample for the forward attention: a scratch pair per length, zeroed ONCE and reused by every span, layer and step (launches on one
-        stream: the next rope_kv overwrites it after the previous flash attention has read it).  Slots past a sample's length hold earlier samples' finite values;
-        the kernel masks them.  Allocating zeroed caches per span was 0.5 GB of fills per layer at 16 x 2048."""
+        stream: the next rope_kv overwrites it after the previous flash attention has read it).  Slots past a sample's length hold whatever earlier samples left
+        (any values, NaN / Inf included): the kernels mask them, V included.  Allocating zeroed caches per span was 0.5 GB of fills per layer at 16 x 2048."""
         key = (int(s_max), dtype, int(lane))                           # one pair per side stream: samples on different streams run at the same time
         if key not in self._kv_pairs:
             self._kv_pairs[key] = ops.alloc_kv(self.nkv, int(s_max), self.D, dtype, self.device)
