@@ -426,17 +426,13 @@ void Model::encode_images(const void* pixels, int n, void* feats, hipStream_t st
     const int rows = n * Tv;                // token rows incl. CLS
     const int prow = n * P;
     const int srows = n * out_tokens;
-    // workspace carve (element counts)
-    size_t off = 0;
-    auto carve = [&](size_t elems) { size_t o = off; off += (elems * es + 255) / 256 * 256; return o; };
-    const size_t o_patch = carve((size_t)prow * kpad), o_pe = carve((size_t)prow * Dv), o_h = carve((size_t)rows * Dv),
-                 o_x = carve((size_t)rows * Dv), o_qkv = carve((size_t)rows * 3 * Dv), o_attn = carve((size_t)rows * Dv),
-                 o_mlp = carve((size_t)rows * Fv), o_sel = carve((size_t)srows * Dv), o_p1 = carve((size_t)srows * H),
-                 o_p2 = carve((size_t)srows * H);
     const int vh = cfg.v_heads;
-    const size_t aws_floats = dt == kF32 ? decode_attn_ws_floats(Tv, vh, 1, vD) : 0;
-    const size_t o_aws = off; off += aws_floats * 4;
-    if (off > vws.bytes) { LMX_CHECK_HIP(hipStreamSynchronize(st)); vws.ensure(off); }
+    Carve carve;
+    const size_t o_patch = carve((size_t)prow * kpad * es), o_pe = carve((size_t)prow * Dv * es), o_h = carve((size_t)rows * Dv * es),
+                 o_x = carve((size_t)rows * Dv * es), o_qkv = carve((size_t)rows * 3 * Dv * es), o_attn = carve((size_t)rows * Dv * es),
+                 o_mlp = carve((size_t)rows * Fv * es), o_sel = carve((size_t)srows * Dv * es), o_p1 = carve((size_t)srows * H * es),
+                 o_p2 = carve((size_t)srows * H * es), o_aws = carve(dt == kF32 ? decode_attn_ws_floats(Tv, vh, 1, vD) * 4 : 0);
+    if (carve.off > vws.bytes) { LMX_CHECK_HIP(hipStreamSynchronize(st)); vws.ensure(carve.off); }
     const size_t kv_bytes = (size_t)vh * spad * vD * es;
     if (vkc.bytes < kv_bytes * n) {
         LMX_CHECK_HIP(hipStreamSynchronize(st));
@@ -531,11 +527,10 @@ Seq::Seq(Model* mm) : m(mm) {
     const int es = m->es;
     n_split = (m->s_max + 127) / 128;          // fixed 128-key chunks (attention.hip: DF_CHUNK)
     const size_t aws = decode_fused_ws_floats(m->nh_l, n_split, m->D);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    Carve carve;
     const size_t o_h = carve((size_t)m->H * es), o_qkv = carve((size_t)m->qkv_n * es), o_attn = carve((size_t)m->nh_l * m->D * es),
                  o_act = carve((size_t)m->I_l * es), o_log = carve((size_t)m->V * es), o_aws = carve(aws * 4), o_cnt = carve((size_t)m->nh_l * 4);
-    dws.ensure(off, true);
+    dws.ensure(carve.off, true);
     char* W = dws.as<char>();
     d_h = W + o_h; d_qkv = W + o_qkv; d_attn = W + o_attn; d_act = W + o_act; d_logits = W + o_log;
     d_aws = reinterpret_cast<float*>(W + o_aws);
@@ -555,152 +550,162 @@ Seq::~Seq() {
 // ---------------------------------------------------------------------------------------------------------------
 // prefill
 // ---------------------------------------------------------------------------------------------------------------
+Model::PrefillWs Model::prefill_ws(Seq* owner, int rows, hipStream_t st) {
+    const int dt = cfg.dtype;
+    Carve carve;
+    const size_t o_h = carve((size_t)rows * H * es), o_x = carve((size_t)rows * H * es), o_qkv = carve((size_t)rows * qkv_n * es),
+                 o_attn = carve((size_t)rows * nh_l * D * es), o_act = carve((size_t)rows * I_l * es),
+                 o_aws = carve(dt == kF32 ? decode_attn_ws_floats(rows, nh_l, 1, D) * 4 : 0), o_log = carve((size_t)V * es);
+    if (carve.off > owner->pws.bytes) { LMX_CHECK_HIP(hipStreamSynchronize(st)); owner->pws.ensure(carve.off); }
+    // N = hidden linears (o_proj, down_proj) give too few 256x256 tiles at prompt lengths around 1k: the ping-pong GEMM slices K
+    // over up to three workgroups per tile and reduces fp32 partial tiles in the launch (gemm8p.hip).  The scratch is per sequence
+    // (request threads prefill concurrently); <= 256 partial tiles = 64 MiB by construction of gemm8p_pick_split.
+    if (dt != kF32 && !owner->skw.p) {
+        LMX_CHECK_HIP(hipStreamSynchronize(st));
+        owner->skw.ensure((size_t)256 * 256 * 256 * sizeof(float));
+    }
+    char* W = owner->pws.as<char>();
+    return PrefillWs{W + o_h, W + o_x, W + o_qkv, W + o_attn, W + o_act, W + o_log, reinterpret_cast<float*>(W + o_aws), owner->skw.p};
+}
+
+// Every linear of a piece is a single GEMM over the piece's rows (a 512-row chunk of one request reaches ~0.19 of the MFMA peak, 4096 packed rows
+// ~0.4); RoPE / KV append / causal attention run per segment against that segment's own cache.
+void Model::prefill_piece(const PrefillWs& ws, const std::vector<PrefillSeg>& seg, int rows, const PieceOpts& o, hipStream_t st) {
+    const int dt = cfg.dtype;
+    const float scale = 1.f / sqrtf((float)D);
+    const int gv = cfg.gemm_variant;
+    const bool lead = cfg.tp_rank == 0;
+    auto with_scratch = [&](GemmArgs g) { g.skw = ws.skw; return g; };
+    auto at = [&](void* base, int r0, size_t width) { return static_cast<char*>(base) + (size_t)r0 * width * es; };
+    for (const PrefillSeg& g : seg) LMX_CHECK_HIP(hipMemcpyAsync(at(ws.h, g.row0, H), g.src, (size_t)g.n * H * es, hipMemcpyDeviceToDevice, st));
+    // rows [r0, r0+n) of the piece through the attention block / the MLP block of layer l (partial sums land in h)
+    auto attn_block = [&](int l, int r0, int n) {
+        const DecLayerW& w = dec[l];
+        auto kc = [&](const Seq* s) { return s->kc.as<char>() + (size_t)l * s->layer_stride; };
+        auto vt = [&](const Seq* s) { return s->vt.as<char>() + (size_t)l * s->layer_stride; };
+        void *hr = at(ws.h, r0, H), *xr = at(ws.x, r0, H), *qr = at(ws.qkv, r0, qkv_n), *ar = at(ws.attn, r0, (size_t)nh_l * D);
+        { LMX_PROF("prefill.rmsnorm"); launch_rmsnorm(dt, hr, w.ln1, xr, n, H, H, H, cfg.rms_eps, st); }
+        // RoPE + KV-cache append ride in the q|k|v GEMM's epilogue where that launch is the un-split ping-pong kernel over head-aligned tiles
+        const PrefillSeg& g0 = seg[0];
+        const int qpos = g0.pos0 + r0 - g0.row0;
+        const bool qf = o.fuse_rope && seg.size() == 1 && gv == 0 && opt_fuse_rope && gemm_fuses_qkv(dt, n, H, D, nh_l, nkv_l, qpos, s_max, false);
+        {
+            LMX_PROF_K("prefill.gemm.qkv");
+            GemmArgs g = with_scratch(GemmArgs{xr, w.wqkv, qr, nullptr, nullptr, n, qkv_n, H, H, H, qkv_n, 0, kActNone});
+            if (qf) { g.qf_rope = rope; g.qf_kc = kc(g0.s); g.qf_vt = vt(g0.s); g.qf_pos0 = qpos; g.qf_nh = nh_l; g.qf_nkv = nkv_l; g.qf_smax = s_max; g.qf_D = D; }
+            launch_gemm(dt, g, gv, st);
+        }
+        for (const PrefillSeg& g : seg) {       // the segment's rows in [r0, r0 + n): rows [a, a + m) of the piece, first position pos
+            const int a = std::max(r0, g.row0), m = std::min(r0 + n, g.row0 + g.n) - a, pos = g.pos0 + a - g.row0;
+            if (m <= 0) continue;
+            void *qa = at(ws.qkv, a, qkv_n), *aa = at(ws.attn, a, (size_t)nh_l * D), *kca = kc(g.s), *vta = vt(g.s);
+            if (!qf) { LMX_PROF("prefill.rope_kv"); launch_rope_kv(dt, D, RopeKvArgs{qa, kca, vta, rope, nullptr, pos, m, qkv_n, nh_l, nkv_l, s_max}, st); }
+            if (o.attn_probs) {
+                void* pl = static_cast<char*>(o.attn_probs) + (size_t)l * nh_l * o.probs_T * o.kv_after * es;
+                launch_attn_probs(dt, D, AttnProbsArgs{qa, kca, pl, m, o.probs_c0 + a, o.probs_T, pos, o.kv_after, qkv_n, nh_l, nkv_l, s_max, scale}, st);
+            }
+            LMX_PROF("prefill.attn");
+            if (dt == kF32) launch_decode_attn(dt, D, DecodeAttnArgs{qa, aa, kca, vta, nullptr, pos, m, 0, 1, qkv_n, nh_l * D, nh_l, nkv_l, s_max, 1, scale, ws.aws}, st);
+            else launch_flash_prefill(dt, D, FlashArgs{qa, aa, kca, vta, m, pos + m, pos, qkv_n, nh_l * D, nh_l, nkv_l, s_max, scale, 1}, st);
+        }
+        { LMX_PROF_K("prefill.gemm.o"); launch_gemm(dt, with_scratch(GemmArgs{ar, w.wo, hr, nullptr, lead ? hr : nullptr, n, H, nh_l * D, nh_l * D, nh_l * D, H, H, kActNone}), gv, st); }
+    };
+    auto mlp_block = [&](int l, int r0, int n) {
+        const DecLayerW& w = dec[l];
+        void *hr = at(ws.h, r0, H), *xr = at(ws.x, r0, H), *cr = at(ws.act, r0, I_l);
+        { LMX_PROF("prefill.rmsnorm"); launch_rmsnorm(dt, hr, w.ln2, xr, n, H, H, H, cfg.rms_eps, st); }
+        { LMX_PROF_K("prefill.gemm.gate_up"); launch_gemm(dt, with_scratch(GemmArgs{xr, w.wgu, cr, nullptr, nullptr, n, 2 * I_l, H, H, H, I_l, 0, kActSiluMul}), gv, st); }
+        { LMX_PROF_K("prefill.gemm.down"); launch_gemm(dt, with_scratch(GemmArgs{cr, w.wd, hr, nullptr, lead ? hr : nullptr, n, H, I_l, I_l, I_l, H, H, kActNone}), gv, st); }
+    };
+    // The two-half pipeline hides 35-55 % of the all-reduce time but costs GEMM efficiency (each half alone cannot fill the chip): measured with a
+    // timed stand-in all-reduce (tools/mb_tp_overlap.py, 7B shards) it wins from rows x ranks >= 4096 on — TP=2 at 2048 rows, TP=8 at 1087 —
+    // and loses below (TP=2 at 1087 rows: 17.7 vs 15.0 ms serialised).  LMX_TP_OVERLAP=2 forces it (tests), =0 switches it off.
+    // With the two-shot peer-to-peer all-reduce (p2p.hip: ~25 us per 8.9 MB message instead of ~114 us on a ring) the sums are 1.6 ms of a TP = 8 prefill:
+    // splitting the piece to hide them costs more GEMM efficiency than it can win, so the pipeline is only for the RCCL path (or forced).
+    const bool tp_active = cfg.tp_world > 1 || comm != nullptr;
+    const bool big_p2p = p2p_big_usable((size_t)rows * H) && rows > P2P_MAX_ROWS && !ar_hook;
+    if (o.tp_pipeline && tp_active && tp_overlap && rows >= 256 && !o.hidden && !o.attn_probs &&
+        (tp_overlap_force || (!big_p2p && (long)rows * std::max(cfg.tp_world, 1) >= 4096))) {
+        // Tensor parallel: the piece runs as two row halves so that the all-reduce of one half (comm stream) overlaps the
+        // GEMMs / attention of the other (launch stream).  Half 1's causal attention sees half 0's keys: same-stream order.
+        Seq* s = seg[0].s;                  // its events order the two streams
+        ensure_comm_stream();
+        s->ensure_events();
+        const int half0 = round_up((rows + 1) / 2, 128) < rows ? round_up((rows + 1) / 2, 128) : rows / 2;
+        const int r0[2] = {0, half0}, rn[2] = {half0, rows - half0};
+        auto reduce_async = [&](int i) {
+            LMX_CHECK_HIP(hipEventRecord(s->ev_c[i], st));
+            LMX_CHECK_HIP(hipStreamWaitEvent(comm_stream, s->ev_c[i], 0));
+            { ProfScope ps(this, "prefill.allreduce", comm_stream); allreduce(at(ws.h, r0[i], H), (size_t)rn[i] * H, comm_stream); }
+            LMX_CHECK_HIP(hipEventRecord(s->ev_r[i], comm_stream));
+        };
+        for (int l = 0; l < L; ++l) {
+            for (int i = 0; i < 2; ++i) {
+                if (l > 0) LMX_CHECK_HIP(hipStreamWaitEvent(st, s->ev_r[i], 0));      // previous layer's MLP sum of this half
+                attn_block(l, r0[i], rn[i]);
+                reduce_async(i);
+            }
+            for (int i = 0; i < 2; ++i) {
+                LMX_CHECK_HIP(hipStreamWaitEvent(st, s->ev_r[i], 0));
+                mlp_block(l, r0[i], rn[i]);
+                reduce_async(i);
+            }
+        }
+        for (int i = 0; i < 2; ++i) LMX_CHECK_HIP(hipStreamWaitEvent(st, s->ev_r[i], 0));
+        return;
+    }
+    // output_hidden_states: the piece's rows of entry e of the tuple
+    auto hidden_rows = [&](int e) { return static_cast<char*>(o.hidden) + (size_t)e * o.hidden_T * H * es; };
+    for (int l = 0; l < L; ++l) {
+        if (o.hidden) LMX_CHECK_HIP(hipMemcpyAsync(hidden_rows(l), ws.h, (size_t)rows * H * es, hipMemcpyDeviceToDevice, st));      // the layer's input rows
+        attn_block(l, 0, rows);
+        allreduce(ws.h, (size_t)rows * H, st);
+        mlp_block(l, 0, rows);
+        { LMX_PROF_AR("prefill.allreduce"); allreduce(ws.h, (size_t)rows * H, st); }
+    }
+    if (o.hidden) launch_rmsnorm(dt, ws.h, final_norm, hidden_rows(L), rows, H, H, H, cfg.rms_eps, st);       // the tuple's last entry is normalised
+}
+
+void Model::prefill_head(Seq* s, const void* h_row, void* dst, bool pick, hipStream_t st) {
+    const int dt = cfg.dtype;
+    // vocabulary-parallel head: this rank computes columns [v_off, v_off + V_l) of a zeroed row, the sum over ranks completes it
+    if (V_l != V) LMX_CHECK_HIP(hipMemsetAsync(dst, 0, (size_t)V * es, st));
+    { LMX_PROF_K("prefill.gemv.lm_head"); launch_gemv(dt, GemvArgs{h_row, lm_head, static_cast<char*>(dst) + (size_t)v_off * es, nullptr, nullptr, final_norm, cfg.rms_eps, V_l, H, H, H, V, 0, kActNone}, 1, st); }
+    gather_logits(dst, 1, st);
+    if (!pick) return;
+    if (s->samp.temperature > 0.f) launch_sample(dt, dst, Vr, s->samp, s->d_nout, s->d_tok, nullptr, nullptr, st);
+    else launch_argmax(dt, dst, Vr, s->d_tok, st);
+    launch_log_token(s->d_tok, s->d_log, s->d_nout, s->log_cap, s->d_stop, st);
+}
+
+// One sequence in pieces of `chunk` rows: each piece is one segment, which may fuse RoPE into the q|k|v GEMM and take the two-half pipeline
 void Model::prefill(Seq* s, const void* embeds, int T, int chunk, void* logits, bool logits_all, bool greedy, hipStream_t st, void* hidden, void* attn_probs) {
     LMX_REQUIRE(T > 0 && embeds, "prefill: empty input");
     LMX_REQUIRE(!attn_probs || (cfg.tp_world == 1 && comm == nullptr), "output_attentions: single process only (a tensor-parallel rank holds a slice of the heads)");
-    const int kv_after = s->len + T;                        // key range of the attention maps' rows: [0, len + T)
     LMX_REQUIRE(s->len + T <= s_max, "prefill: sequence would exceed the KV-cache capacity (max_position)");
     LMX_REQUIRE(rope != nullptr, "rope table not set");
     s->last_stream = st; s->used = true;
     if (chunk <= 0 || chunk > T) chunk = T;
     const int dt = cfg.dtype;
-    // workspace
-    {
-        size_t off = 0;
-        auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-        const size_t aws = dt == kF32 ? decode_attn_ws_floats(chunk, nh_l, 1, D) * 4 : 0;
-        carve((size_t)chunk * H * es); carve((size_t)chunk * H * es); carve((size_t)chunk * qkv_n * es);
-        carve((size_t)chunk * nh_l * D * es); carve((size_t)chunk * I_l * es); carve(aws); carve((size_t)V * es);
-        if (off > s->pws.bytes) { LMX_CHECK_HIP(hipStreamSynchronize(st)); s->pws.ensure(off); }
-    }
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    char* W = s->pws.as<char>();
-    void* h = W + carve((size_t)chunk * H * es);
-    void* x = W + carve((size_t)chunk * H * es);
-    void* qkv = W + carve((size_t)chunk * qkv_n * es);
-    void* attn = W + carve((size_t)chunk * nh_l * D * es);
-    void* act = W + carve((size_t)chunk * I_l * es);
-    float* aws = reinterpret_cast<float*>(W + carve(dt == kF32 ? decode_attn_ws_floats(chunk, nh_l, 1, D) * 4 : 0));
-    void* last_logits = W + carve((size_t)V * es);
-    const float scale = 1.f / sqrtf((float)D);
-    const int gv = cfg.gemm_variant;
-    const bool lead = cfg.tp_rank == 0;
-    // N = hidden linears (o_proj, down_proj) give too few 256x256 tiles at prompt lengths around 1k: the ping-pong GEMM slices K
-    // over up to three workgroups per tile and reduces fp32 partial tiles in the launch (gemm8p.hip).  The scratch is per sequence
-    // (request threads prefill concurrently); <= 256 partial tiles = 64 MiB by construction of gemm8p_pick_split.
-    if (dt != kF32 && !s->skw.p) {
-        LMX_CHECK_HIP(hipStreamSynchronize(st));
-        s->skw.ensure((size_t)256 * 256 * 256 * sizeof(float));
-    }
-    auto with_scratch = [&](GemmArgs g) { g.skw = s->skw.p; return g; };
-
+    const PrefillWs ws = prefill_ws(s, chunk, st);
+    PieceOpts o;
+    o.fuse_rope = o.tp_pipeline = true;
+    o.hidden_T = o.probs_T = T;
+    o.attn_probs = attn_probs; o.kv_after = s->len + T;      // key range of the attention maps' rows: [0, len + T)
     for (int c0 = 0; c0 < T; c0 += chunk) {
         const int tc = (T - c0) < chunk ? (T - c0) : chunk;
-        const int pos0 = s->len + c0;
-        LMX_CHECK_HIP(hipMemcpyAsync(h, static_cast<const char*>(embeds) + (size_t)c0 * H * es, (size_t)tc * H * es, hipMemcpyDeviceToDevice, st));
-        // rows [r0, r0+n) of this chunk through the attention block / the MLP block of layer l (partial sums land in h)
-        auto rows = [&](void* base, int r0, size_t width) { return static_cast<char*>(base) + (size_t)r0 * width * es; };
-        const bool tp_active = cfg.tp_world > 1 || comm != nullptr;
-        auto attn_block = [&](int l, int r0, int n) {
-            const DecLayerW& w = dec[l];
-            void* kc = s->kc.as<char>() + (size_t)l * s->layer_stride;
-            void* vt = s->vt.as<char>() + (size_t)l * s->layer_stride;
-            void *hr = rows(h, r0, H), *xr = rows(x, r0, H), *qr = rows(qkv, r0, qkv_n), *ar = rows(attn, r0, (size_t)nh_l * D);
-            { LMX_PROF("prefill.rmsnorm"); launch_rmsnorm(dt, hr, w.ln1, xr, n, H, H, H, cfg.rms_eps, st); }
-            // RoPE + KV-cache append ride in the q|k|v GEMM's epilogue where that launch is the un-split ping-pong kernel over head-aligned tiles
-            const bool qf = gv == 0 && opt_fuse_rope && gemm_fuses_qkv(dt, n, H, D, nh_l, nkv_l, pos0 + r0, s_max, false);
-            {
-                LMX_PROF_K("prefill.gemm.qkv");
-                GemmArgs g = with_scratch(GemmArgs{xr, w.wqkv, qr, nullptr, nullptr, n, qkv_n, H, H, H, qkv_n, 0, kActNone});
-                if (qf) { g.qf_rope = rope; g.qf_kc = kc; g.qf_vt = vt; g.qf_pos0 = pos0 + r0; g.qf_nh = nh_l; g.qf_nkv = nkv_l; g.qf_smax = s_max; g.qf_D = D; }
-                launch_gemm(dt, g, gv, st);
-            }
-            if (!qf) { LMX_PROF("prefill.rope_kv"); launch_rope_kv(dt, D, RopeKvArgs{qr, kc, vt, rope, nullptr, pos0 + r0, n, qkv_n, nh_l, nkv_l, s_max}, st); }
-            if (attn_probs) {
-                void* pl = static_cast<char*>(attn_probs) + (size_t)l * nh_l * T * kv_after * es;
-                launch_attn_probs(dt, D, AttnProbsArgs{qr, kc, pl, n, c0 + r0, T, pos0 + r0, kv_after, qkv_n, nh_l, nkv_l, s_max, scale}, st);
-            }
-            if (dt == kF32) {
-                { LMX_PROF("prefill.attn"); launch_decode_attn(dt, D, DecodeAttnArgs{qr, ar, kc, vt, nullptr, pos0 + r0, n, 0, 1, qkv_n, nh_l * D, nh_l, nkv_l, s_max, 1, scale, aws}, st); }
-            } else {
-                { LMX_PROF("prefill.attn"); launch_flash_prefill(dt, D, FlashArgs{qr, ar, kc, vt, n, pos0 + r0 + n, pos0 + r0, qkv_n, nh_l * D, nh_l, nkv_l, s_max, scale, 1}, st); }
-            }
-            { LMX_PROF_K("prefill.gemm.o"); launch_gemm(dt, with_scratch(GemmArgs{ar, w.wo, hr, nullptr, lead ? hr : nullptr, n, H, nh_l * D, nh_l * D, nh_l * D, H, H, kActNone}), gv, st); }
-        };
-        auto mlp_block = [&](int l, int r0, int n) {
-            const DecLayerW& w = dec[l];
-            void *hr = rows(h, r0, H), *xr = rows(x, r0, H), *cr = rows(act, r0, I_l);
-            { LMX_PROF("prefill.rmsnorm"); launch_rmsnorm(dt, hr, w.ln2, xr, n, H, H, H, cfg.rms_eps, st); }
-            { LMX_PROF_K("prefill.gemm.gate_up"); launch_gemm(dt, with_scratch(GemmArgs{xr, w.wgu, cr, nullptr, nullptr, n, 2 * I_l, H, H, H, I_l, 0, kActSiluMul}), gv, st); }
-            { LMX_PROF_K("prefill.gemm.down"); launch_gemm(dt, with_scratch(GemmArgs{cr, w.wd, hr, nullptr, lead ? hr : nullptr, n, H, I_l, I_l, I_l, H, H, kActNone}), gv, st); }
-        };
-        // The two-half pipeline hides 35-55 % of the all-reduce time but costs GEMM efficiency (each half alone cannot fill the chip): measured with a
-        // timed stand-in all-reduce (tools/mb_tp_overlap.py, 7B shards) it wins from rows x ranks >= 4096 on — TP=2 at 2048 rows, TP=8 at 1087 —
-        // and loses below (TP=2 at 1087 rows: 17.7 vs 15.0 ms serialised).  LMX_TP_OVERLAP=2 forces it (tests), =0 switches it off.
-        // output_hidden_states: rows [c0, c0 + tc) of entry e of the [L + 1][T][H] tuple
-        auto hidden_rows = [&](int e) { return static_cast<char*>(hidden) + ((size_t)e * T + c0) * H * es; };
-        // With the two-shot peer-to-peer all-reduce (p2p.hip: ~25 us per 8.9 MB message instead of ~114 us on a ring) the sums are 1.6 ms of a TP = 8 prefill:
-        // splitting the chunk to hide them costs more GEMM efficiency than it can win, so the pipeline is only for the RCCL path (or forced).
-        const bool big_p2p = p2p_big_usable((size_t)tc * H) && tc > P2P_MAX_ROWS && !ar_hook;
-        if (tp_active && tp_overlap && tc >= 256 && !hidden && !attn_probs && (tp_overlap_force || (!big_p2p && (long)tc * std::max(cfg.tp_world, 1) >= 4096))) {
-            // Tensor parallel: the chunk runs as two row halves so that the all-reduce of one half (comm stream) overlaps the
-            // GEMMs / attention of the other (launch stream).  Half 1's causal attention sees half 0's keys: same-stream order.
-            ensure_comm_stream();
-            s->ensure_events();
-            const int half0 = round_up((tc + 1) / 2, 128) < tc ? round_up((tc + 1) / 2, 128) : tc / 2;
-            const int r0[2] = {0, half0}, rn[2] = {half0, tc - half0};
-            auto reduce_async = [&](int i) {
-                LMX_CHECK_HIP(hipEventRecord(s->ev_c[i], st));
-                LMX_CHECK_HIP(hipStreamWaitEvent(comm_stream, s->ev_c[i], 0));
-                { ProfScope ps(this, "prefill.allreduce", comm_stream); allreduce(rows(h, r0[i], H), (size_t)rn[i] * H, comm_stream); }
-                LMX_CHECK_HIP(hipEventRecord(s->ev_r[i], comm_stream));
-            };
-            for (int l = 0; l < L; ++l) {
-                for (int i = 0; i < 2; ++i) {
-                    if (l > 0) LMX_CHECK_HIP(hipStreamWaitEvent(st, s->ev_r[i], 0));      // previous layer's MLP sum of this half
-                    attn_block(l, r0[i], rn[i]);
-                    reduce_async(i);
-                }
-                for (int i = 0; i < 2; ++i) {
-                    LMX_CHECK_HIP(hipStreamWaitEvent(st, s->ev_r[i], 0));
-                    mlp_block(l, r0[i], rn[i]);
-                    reduce_async(i);
-                }
-            }
-            for (int i = 0; i < 2; ++i) LMX_CHECK_HIP(hipStreamWaitEvent(st, s->ev_r[i], 0));
-        } else {
-            for (int l = 0; l < L; ++l) {
-                if (hidden) LMX_CHECK_HIP(hipMemcpyAsync(hidden_rows(l), h, (size_t)tc * H * es, hipMemcpyDeviceToDevice, st));      // the layer's input rows
-                attn_block(l, 0, tc);
-                allreduce(h, (size_t)tc * H, st);
-                mlp_block(l, 0, tc);
-                { LMX_PROF_AR("prefill.allreduce"); allreduce(h, (size_t)tc * H, st); }
-            }
-            if (hidden) launch_rmsnorm(dt, h, final_norm, hidden_rows(L), tc, H, H, H, cfg.rms_eps, st);       // the tuple's last entry is normalised
-        }
-        const bool last_chunk = c0 + tc == T;
-        // vocabulary-parallel head: this rank computes columns [v_off, v_off + V_l) of a zeroed row, the sum over ranks completes it
-        const bool vsplit = V_l != V;
+        o.hidden = hidden ? static_cast<char*>(hidden) + (size_t)c0 * H * es : nullptr;
+        o.probs_c0 = c0;
+        prefill_piece(ws, {PrefillSeg{s, 0, tc, s->len + c0, static_cast<const char*>(embeds) + (size_t)c0 * H * es}}, tc, o, st);
         if (logits_all && logits) {
             char* lc = static_cast<char*>(logits) + (size_t)c0 * V * es;
-            launch_rmsnorm(dt, h, final_norm, x, tc, H, H, H, cfg.rms_eps, st);
-            if (vsplit) LMX_CHECK_HIP(hipMemsetAsync(lc, 0, (size_t)tc * V * es, st));
-            launch_gemm(dt, GemmArgs{x, lm_head, lc + (size_t)v_off * es, nullptr, nullptr, tc, V_l, H, H, H, V, 0, kActNone}, gv, st);
+            launch_rmsnorm(dt, ws.h, final_norm, ws.x, tc, H, H, H, cfg.rms_eps, st);
+            if (V_l != V) LMX_CHECK_HIP(hipMemsetAsync(lc, 0, (size_t)tc * V * es, st));
+            launch_gemm(dt, GemmArgs{ws.x, lm_head, lc + (size_t)v_off * es, nullptr, nullptr, tc, V_l, H, H, H, V, 0, kActNone}, cfg.gemm_variant, st);
             gather_logits(lc, tc, st);
         }
-        if (last_chunk && (greedy || (logits && !logits_all))) {
-            const void* hl = static_cast<const char*>(h) + (size_t)(tc - 1) * H * es;
-            void* dst = (logits && !logits_all) ? logits : last_logits;
-            if (vsplit) LMX_CHECK_HIP(hipMemsetAsync(dst, 0, (size_t)V * es, st));
-            { LMX_PROF_K("prefill.gemv.lm_head"); launch_gemv(dt, GemvArgs{hl, lm_head, static_cast<char*>(dst) + (size_t)v_off * es, nullptr, nullptr, final_norm, cfg.rms_eps, V_l, H, H, H, V, 0, kActNone}, 1, st); }
-            gather_logits(dst, 1, st);
-            if (greedy) {
-                if (s->samp.temperature > 0.f) launch_sample(dt, dst, Vr, s->samp, s->d_nout, s->d_tok, nullptr, nullptr, st);
-                else launch_argmax(dt, dst, Vr, s->d_tok, st);
-                launch_log_token(s->d_tok, s->d_log, s->d_nout, s->log_cap, s->d_stop, st);
-            }
-        }
+        if (c0 + tc == T && (greedy || (logits && !logits_all)))
+            prefill_head(s, static_cast<char*>(ws.h) + (size_t)(tc - 1) * H * es, (logits && !logits_all) ? logits : ws.last_logits, greedy, st);
     }
     s->len += T;
     launch_set_state(s->d_len, s->len, s->d_tok, 0, 0, s->d_nout, -1, st);
@@ -709,11 +714,10 @@ void Model::prefill(Seq* s, const void* embeds, int T, int chunk, void* logits, 
 // ---------------------------------------------------------------------------------------------------------------
 // packed prefill of several sequences (serving: BASELINE configs 3 / 4 prefill many requests at once)
 // ---------------------------------------------------------------------------------------------------------------
-// The rows of all sequences are walked as ONE packed row block in pieces of `block_rows`: every linear of a piece is a single GEMM over the piece's
-// rows (a 512-row chunk of one request reaches ~0.19 of the MFMA peak, 4096 packed rows ~0.4), RoPE / KV append / causal attention run per
-// (sequence, row range) segment against that sequence's own cache, as in the chunked prefill of one sequence.  The row arithmetic is unchanged, so a
-// sequence's result does not depend on who shares the piece with it (up to the split-K choice of the N = hidden GEMMs, which changes the summation
-// order of their fp32 partial sums).  Each sequence's last row goes through the lm_head and its pick, exactly as Model::prefill does.
+// The rows of all sequences are walked as ONE packed row block in pieces of `block_rows`, one segment per (sequence, row range) in a piece, as in the
+// chunked prefill of one sequence.  The row arithmetic is unchanged, so a sequence's result does not depend on who shares the piece with it (up to the
+// split-K choice of the N = hidden GEMMs, which changes the summation order of their fp32 partial sums).  Each sequence's last row goes through the
+// lm_head and its pick, exactly as Model::prefill does.
 void Model::prefill_multi(Seq* const* seqs, const void* const* embeds, const int* Ts, int n, int block_rows, bool greedy, hipStream_t st) {
     LMX_REQUIRE(n >= 1 && seqs && embeds && Ts, "prefill_multi: bad arguments");
     LMX_REQUIRE(rope != nullptr, "rope table not set");
@@ -726,73 +730,21 @@ void Model::prefill_multi(Seq* const* seqs, const void* const* embeds, const int
         total += Ts[i];
     }
     if (block_rows <= 0 || block_rows > total) block_rows = (int)total;
-    const int dt = cfg.dtype;
-    Seq* s0 = seqs[0];                                   // owner of the piece workspace and the split-K scratch of this call
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_h = carve((size_t)block_rows * H * es), o_x = carve((size_t)block_rows * H * es), o_qkv = carve((size_t)block_rows * qkv_n * es),
-                 o_attn = carve((size_t)block_rows * nh_l * D * es), o_act = carve((size_t)block_rows * I_l * es),
-                 o_aws = carve(dt == kF32 ? decode_attn_ws_floats(block_rows, nh_l, 1, D) * 4 : 0), o_log = carve((size_t)V * es);
-    if (off > s0->pws.bytes) { LMX_CHECK_HIP(hipStreamSynchronize(st)); s0->pws.ensure(off); }
-    char* W = s0->pws.as<char>();
-    void *h = W + o_h, *x = W + o_x, *qkv = W + o_qkv, *attn = W + o_attn, *act = W + o_act, *last_logits = W + o_log;
-    float* aws = reinterpret_cast<float*>(W + o_aws);
-    const float scale = 1.f / sqrtf((float)D);
-    const int gv = cfg.gemm_variant;
-    const bool lead = cfg.tp_rank == 0;
-    if (dt != kF32 && !s0->skw.p) {
-        LMX_CHECK_HIP(hipStreamSynchronize(st));
-        s0->skw.ensure((size_t)256 * 256 * 256 * sizeof(float));
-    }
-    auto with_scratch = [&](GemmArgs g) { g.skw = s0->skw.p; return g; };
-    auto rows = [&](void* base, long r0, size_t width) { return static_cast<char*>(base) + (size_t)r0 * width * es; };
-    struct Segment { int seq, src0, dst0, n, pos0; };    // rows [src0, src0 + n) of sequence `seq` sit at rows [dst0, ...) of the piece; first position pos0
-    int cur = 0, cur_done = 0;                           // next sequence / rows of it already consumed
-    const bool vsplit = V_l != V;
+    const PrefillWs ws = prefill_ws(seqs[0], block_rows, st);      // the first sequence owns the piece workspace and the split-K scratch of this call
+    int cur = 0, cur_done = 0;                                       // next sequence / rows of it already consumed
     while (cur < n) {
-        std::vector<Segment> seg;
+        std::vector<PrefillSeg> seg;
+        std::vector<int> ends;                                       // segments whose sequence ends in this piece
         int fill = 0;
         while (cur < n && fill < block_rows) {
             const int take = std::min(block_rows - fill, Ts[cur] - cur_done);
-            seg.push_back(Segment{cur, cur_done, fill, take, seqs[cur]->len + cur_done});
+            seg.push_back(PrefillSeg{seqs[cur], fill, take, seqs[cur]->len + cur_done, static_cast<const char*>(embeds[cur]) + (size_t)cur_done * H * es});
             fill += take; cur_done += take;
-            if (cur_done == Ts[cur]) { ++cur; cur_done = 0; }
+            if (cur_done == Ts[cur]) { ends.push_back((int)seg.size() - 1); ++cur; cur_done = 0; }
         }
-        for (const Segment& g : seg)
-            LMX_CHECK_HIP(hipMemcpyAsync(rows(h, g.dst0, H), static_cast<const char*>(embeds[g.seq]) + (size_t)g.src0 * H * es, (size_t)g.n * H * es, hipMemcpyDeviceToDevice, st));
-        for (int l = 0; l < L; ++l) {
-            const DecLayerW& w = dec[l];
-            { LMX_PROF("prefill.rmsnorm"); launch_rmsnorm(dt, h, w.ln1, x, fill, H, H, H, cfg.rms_eps, st); }
-            { LMX_PROF_K("prefill.gemm.qkv"); launch_gemm(dt, with_scratch(GemmArgs{x, w.wqkv, qkv, nullptr, nullptr, fill, qkv_n, H, H, H, qkv_n, 0, kActNone}), gv, st); }
-            for (const Segment& g : seg) {
-                Seq* s = seqs[g.seq];
-                void* kc = s->kc.as<char>() + (size_t)l * s->layer_stride;
-                void* vt = s->vt.as<char>() + (size_t)l * s->layer_stride;
-                void *qr = rows(qkv, g.dst0, qkv_n), *ar = rows(attn, g.dst0, (size_t)nh_l * D);
-                { LMX_PROF("prefill.rope_kv"); launch_rope_kv(dt, D, RopeKvArgs{qr, kc, vt, rope, nullptr, g.pos0, g.n, qkv_n, nh_l, nkv_l, s_max}, st); }
-                LMX_PROF("prefill.attn");
-                if (dt == kF32) launch_decode_attn(dt, D, DecodeAttnArgs{qr, ar, kc, vt, nullptr, g.pos0, g.n, 0, 1, qkv_n, nh_l * D, nh_l, nkv_l, s_max, 1, scale, aws}, st);
-                else launch_flash_prefill(dt, D, FlashArgs{qr, ar, kc, vt, g.n, g.pos0 + g.n, g.pos0, qkv_n, nh_l * D, nh_l, nkv_l, s_max, scale, 1}, st);
-            }
-            { LMX_PROF_K("prefill.gemm.o"); launch_gemm(dt, with_scratch(GemmArgs{attn, w.wo, h, nullptr, lead ? h : nullptr, fill, H, nh_l * D, nh_l * D, nh_l * D, H, H, kActNone}), gv, st); }
-            allreduce(h, (size_t)fill * H, st);
-            { LMX_PROF("prefill.rmsnorm"); launch_rmsnorm(dt, h, w.ln2, x, fill, H, H, H, cfg.rms_eps, st); }
-            { LMX_PROF_K("prefill.gemm.gate_up"); launch_gemm(dt, with_scratch(GemmArgs{x, w.wgu, act, nullptr, nullptr, fill, 2 * I_l, H, H, H, I_l, 0, kActSiluMul}), gv, st); }
-            { LMX_PROF_K("prefill.gemm.down"); launch_gemm(dt, with_scratch(GemmArgs{act, w.wd, h, nullptr, lead ? h : nullptr, fill, H, I_l, I_l, I_l, H, H, kActNone}), gv, st); }
-            { LMX_PROF_AR("prefill.allreduce"); allreduce(h, (size_t)fill * H, st); }
-        }
-        // sequences that END in this piece: lm_head on their last row + the pick
-        for (const Segment& g : seg) {
-            if (g.src0 + g.n != Ts[g.seq] || !greedy) continue;
-            Seq* s = seqs[g.seq];
-            const void* hl = rows(h, g.dst0 + g.n - 1, H);
-            if (vsplit) LMX_CHECK_HIP(hipMemsetAsync(last_logits, 0, (size_t)V * es, st));
-            { LMX_PROF_K("prefill.gemv.lm_head"); launch_gemv(dt, GemvArgs{hl, lm_head, static_cast<char*>(last_logits) + (size_t)v_off * es, nullptr, nullptr, final_norm, cfg.rms_eps, V_l, H, H, H, V, 0, kActNone}, 1, st); }
-            gather_logits(last_logits, 1, st);
-            if (s->samp.temperature > 0.f) launch_sample(dt, last_logits, Vr, s->samp, s->d_nout, s->d_tok, nullptr, nullptr, st);
-            else launch_argmax(dt, last_logits, Vr, s->d_tok, st);
-            launch_log_token(s->d_tok, s->d_log, s->d_nout, s->log_cap, s->d_stop, st);
-        }
+        prefill_piece(ws, seg, fill, PieceOpts{}, st);      // no fused RoPE, no two-half pipeline
+        if (greedy)
+            for (int e : ends) prefill_head(seg[e].s, static_cast<char*>(ws.h) + (size_t)(seg[e].row0 + seg[e].n - 1) * H * es, ws.last_logits, true, st);
     }
     for (int i = 0; i < n; ++i) {
         seqs[i]->len += Ts[i];
@@ -933,11 +885,10 @@ void Model::ensure_batch_weights(hipStream_t st) {
 Batch::Batch(Model* mm, int capacity) : m(mm), cap(capacity) {
     LMX_REQUIRE(capacity >= 1 && capacity <= 256, "batch capacity must be 1..256");
     const int es = m->es;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    Carve carve;
     const size_t o_h = carve((size_t)cap * m->H * es), o_x = carve((size_t)cap * m->H * es), o_qkv = carve((size_t)cap * m->qkv_n * es),
                  o_attn = carve((size_t)cap * m->nh_l * m->D * es), o_act = carve((size_t)cap * m->I_l * es), o_log = carve((size_t)cap * m->V * es);
-    ws.ensure(off, true);
+    ws.ensure(carve.off, true);
     char* W = ws.as<char>();
     h = W + o_h; x = W + o_x; qkv = W + o_qkv; attn = W + o_attn; act = W + o_act; logits = W + o_log;
     const size_t attn_bytes = sizeof(DecodeFusedSeq) * (size_t)m->L * cap, state_bytes = sizeof(SeqStateRef) * (size_t)cap;

@@ -39,6 +39,12 @@ struct DevBuf {
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// Consecutive regions of one workspace: each call returns the offset of the next region (256-byte aligned); `off` ends as the size of the whole
+struct Carve {
+    size_t off = 0;
+    size_t operator()(size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; }
+};
+
 struct DecLayerW {
     void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr, *ln1 = nullptr, *ln2 = nullptr;
     void *sw_qkv = nullptr, *sw_o = nullptr, *sw_gu = nullptr, *sw_d = nullptr;   // fragment-order copies for the decode-batch kernel
@@ -134,6 +140,20 @@ struct Model {
     void prefill(Seq* s, const void* embeds, int T, int chunk, void* logits, bool logits_all, bool greedy, hipStream_t st, void* hidden = nullptr, void* attn = nullptr);
     void decode(Seq* s, int64_t token, int n_steps, void* logits, bool greedy, hipStream_t st);
     void prefill_multi(Seq* const* seqs, const void* const* embeds, const int* Ts, int n, int block_rows, bool greedy, hipStream_t st);
+    // ---- what both prefills run: a piece of up to `rows` rows through all L layers ----------------------------------------------------------------------
+    struct PrefillWs { void *h, *x, *qkv, *attn, *act, *last_logits; float* aws; void* skw; };
+    PrefillWs prefill_ws(Seq* owner, int rows, hipStream_t st);     // grows owner's pws (and its split-K scratch skw) for pieces of up to `rows` rows
+    // rows [row0, row0 + n) of a piece: positions [pos0, pos0 + n) of sequence s, read from src ([n][H] embeddings)
+    struct PrefillSeg { Seq* s; int row0, n, pos0; const void* src; };
+    struct PieceOpts {
+        bool fuse_rope = false;             // RoPE + KV append in the q|k|v GEMM's epilogue where it applies (one-segment pieces)
+        bool tp_pipeline = false;           // the tensor-parallel two-half pipeline where it pays
+        void* hidden = nullptr; int hidden_T = 0;                          // row 0 of the piece in entry 0 of the [L + 1][hidden_T][H] hidden-states tuple
+        void* attn_probs = nullptr; int probs_c0 = 0, probs_T = 0, kv_after = 0;   // [L][heads][probs_T][kv_after]; the piece's rows start at row probs_c0
+    };
+    void prefill_piece(const PrefillWs& ws, const std::vector<PrefillSeg>& seg, int rows, const PieceOpts& o, hipStream_t st);
+    // lm_head (+ final norm) of one hidden row into dst [V]; pick: s's next token (sample / argmax) and its log entry
+    void prefill_head(Seq* s, const void* h_row, void* dst, bool pick, hipStream_t st);
     void decode_step_launch(Seq* s, hipStream_t st, int64_t* id_out = nullptr);      // id_out (device): this step's picked id, -1 after a device-side stop
     void seq_copy(Seq* dst, const Seq* src, hipStream_t st);      // dst := src's context (KV of the first src->len positions, length): beam reordering
     void decode_batch(struct Batch* b, Seq* const* seqs, int n, const int64_t* tokens, int n_steps, void* logits, bool greedy, int64_t* ids_out_host, hipStream_t st,
@@ -175,7 +195,7 @@ struct Seq {
     int* d_len = nullptr; int* d_nout = nullptr; int64_t* d_tok = nullptr; int64_t* d_log = nullptr;
     DevBuf stopbuf; StopSpec* d_stop = nullptr;          // device-side stop rule (lmx_seq_set_stop); all zero = no rule
     int log_cap = 0;
-    DevBuf pws;  int pws_tokens = 0;   // prefill workspace
+    DevBuf pws;                        // prefill workspace
     DevBuf skw;                        // split-K partial tiles of the ping-pong GEMM (o_proj, down_proj of a prefill)
     DevBuf dws;                        // decode workspace
     void *d_h = nullptr, *d_qkv = nullptr, *d_attn = nullptr, *d_act = nullptr, *d_logits = nullptr; float* d_aws = nullptr; int* d_cnt = nullptr;

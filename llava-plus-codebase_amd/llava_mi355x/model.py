@@ -720,25 +720,49 @@ class LlavaLlamaForCausalLM:
         return None, new_pos, new_mask, past_key_values, embeds, new_labels
 
     # ---- decoder ---------------------------------------------------------------------------------------------------
+    def _valid_rows(self, embeds: torch.Tensor, valid: Optional[torch.Tensor], b: int):
+        """(idx, rows) of row b of [B,T,H] embeddings: `rows` its real (`valid`) positions in order, contiguous, and `idx` their indices —
+        None when every position is real; rows None when none is."""
+        if valid is None:
+            return None, embeds[b].contiguous()
+        idx = torch.nonzero(valid[b].to(self.device), as_tuple=False).flatten()
+        n = int(idx.numel())
+        if n == 0:
+            return None, None
+        if n == embeds.shape[1]:
+            return None, embeds[b].contiguous()
+        return idx, embeds[b].index_select(0, idx).contiguous()
+
+    def _packed_rows(self, embeds: torch.Tensor, valid: Optional[torch.Tensor]) -> torch.Tensor:
+        """Rows of one request (embeds [1,T,H], valid [1,T] or None) for the packed prefill: its valid (non-pad) positions, in order."""
+        e = embeds[0]
+        if valid is not None and not bool(valid[0].all()):
+            e = e.index_select(0, torch.nonzero(valid[0].to(self.device), as_tuple=False).flatten())
+        return e.to(self.dtype).contiguous()
+
+    def _prefill_packed(self, seqs, packed: Sequence[torch.Tensor], prefill_chunk: int = 0):
+        """lmx_prefill_batch: sequence seqs[i] takes rows packed[i] ([T_i, H], _packed_rows); all rows form one packed block walked in pieces of
+        prefill_chunk x requests rows.  The first pick of each sequence is on the device when the stream gets there."""
+        n = len(packed)
+        arr = (ctypes.c_void_p * n)(*[q.value if isinstance(q, ctypes.c_void_p) else q for q in seqs])
+        eptr = (ctypes.c_void_p * n)(*[e.data_ptr() for e in packed])
+        cnt = (ctypes.c_int32 * n)(*[int(e.shape[0]) for e in packed])
+        check(lib.lmx_prefill_batch(self._h, arr, n, eptr, cnt, int(prefill_chunk) * n if prefill_chunk else 0, 1, stream_handle()), "lmx_prefill_batch")
+
     def _prefill_rows(self, cache: LmxKVCache, embeds: torch.Tensor, valid: Optional[torch.Tensor], want_all: bool, greedy: bool, chunk: int = 0):
         """Run the decoder over [B,T,H] embeddings; `valid` [B,T] bool marks real (non-pad) positions."""
         B, T, H = embeds.shape
         V = self._vocab_cap                 # row pitch of the engine's logits; callers slice to config.vocab_size
         logits = torch.zeros((B, T if want_all else 1, V), dtype=self.dtype, device=self.device)
         for b in range(B):
-            if valid is not None:
-                idx = torch.nonzero(valid[b].to(self.device), as_tuple=False).flatten()
-                n = int(idx.numel())
-                if n == 0:
-                    continue
-                e = embeds[b] if n == T else embeds[b].index_select(0, idx).contiguous()
-            else:
-                idx, n, e = None, T, embeds[b]
-            e = e.contiguous()
+            idx, e = self._valid_rows(embeds, valid, b)
+            if e is None:
+                continue
+            n = e.shape[0]
             if want_all:
-                lg = logits[b] if n == T else torch.empty((n, V), dtype=self.dtype, device=self.device)
+                lg = logits[b] if idx is None else torch.empty((n, V), dtype=self.dtype, device=self.device)
                 check(lib.lmx_prefill(self._h, cache.seqs[b], ptr(e), n, chunk, ptr(lg), 1, int(greedy), stream_handle()), "lmx_prefill")
-                if n != T:
+                if idx is not None:
                     logits[b].index_copy_(0, idx, lg)
             else:
                 check(lib.lmx_prefill(self._h, cache.seqs[b], ptr(e), n, chunk, ptr(logits[b]), 0, int(greedy), stream_handle()), "lmx_prefill")
@@ -762,14 +786,9 @@ class LlavaLlamaForCausalLM:
                 raise NotImplementedError("output_attentions with padding on top of a KV cache is not supported (un-padded continuation, or padded batches from an empty cache)")
             attn = torch.zeros((L, B, nh, T, max(past) + T), dtype=self.dtype, device=self.device)
         for b in range(B):
-            idx = None
-            if valid is not None:
-                idx = torch.nonzero(valid[b].to(self.device), as_tuple=False).flatten()
-                if int(idx.numel()) == T:
-                    idx = None
-                elif int(idx.numel()) == 0:
-                    continue
-            e = (embeds[b] if idx is None else embeds[b].index_select(0, idx)).contiguous()
+            idx, e = self._valid_rows(embeds, valid, b)
+            if e is None:
+                continue
             n = e.shape[0]
             lg = torch.empty((n, V), dtype=self.dtype, device=self.device)
             hs = torch.empty((L + 1, n, H), dtype=self.dtype, device=self.device) if want_hidden else None
@@ -959,19 +978,11 @@ class LlavaLlamaForCausalLM:
                     check(lib.lmx_seq_set_sampling(cache.seqs[0], float(temperature), float(top_p if top_p is not None else 1.0), int(top_k or 0), seed),
                           "lmx_seq_set_sampling")
                 if packed_prefill:
-                    # rows of this request for the packed prefill: its valid (non-pad) positions, in order
-                    e = embeds[0]
-                    if valid is not None and not bool(valid[0].all()):
-                        e = e.index_select(0, torch.nonzero(valid[0].to(self.device), as_tuple=False).flatten())
-                    packed.append(e.to(self.dtype).contiguous())
+                    packed.append(self._packed_rows(embeds, valid))
                 else:
                     self._prefill_rows(cache, embeds, valid, want_all=False, greedy=True, chunk=prefill_chunk)
             if packed_prefill:
-                n = len(packed)
-                arr = (ctypes.c_void_p * n)(*[c.seqs[0].value if isinstance(c.seqs[0], ctypes.c_void_p) else c.seqs[0] for c in caches])
-                eptr = (ctypes.c_void_p * n)(*[e.data_ptr() for e in packed])
-                cnt = (ctypes.c_int32 * n)(*[int(e.shape[0]) for e in packed])
-                check(lib.lmx_prefill_batch(self._h, arr, n, eptr, cnt, int(prefill_chunk) * n if prefill_chunk else 0, 1, stream_handle()), "lmx_prefill_batch")
+                self._prefill_packed([c.seqs[0] for c in caches], packed, prefill_chunk)
             for cache in caches:
                 budgets.append(min(max_new_tokens, self.s_max - lib.lmx_seq_length(cache.seqs[0])))
                 host1 = (ctypes.c_int64 * 1)(); n1 = ctypes.c_int32(0)
@@ -1224,18 +1235,7 @@ class LlavaLlamaForCausalLM:
             p = prepared[0]
             last = self._prefill_rows(p["cache"], p["embeds"], p["valid"], want_all=False, greedy=True, chunk=prefill_chunk)
             return last if return_logits else None
-        packed = []
-        for p in prepared:
-            e, valid = p["embeds"][0], p["valid"]
-            if valid is not None and not bool(valid[0].all()):
-                e = e.index_select(0, torch.nonzero(valid[0].to(self.device), as_tuple=False).flatten())
-            packed.append(e.to(self.dtype).contiguous())
-        n = len(prepared)
-        seqs = [p["cache"].seqs[0] for p in prepared]
-        arr = (ctypes.c_void_p * n)(*[q.value if isinstance(q, ctypes.c_void_p) else q for q in seqs])
-        eptr = (ctypes.c_void_p * n)(*[e.data_ptr() for e in packed])
-        cnt = (ctypes.c_int32 * n)(*[int(e.shape[0]) for e in packed])
-        check(lib.lmx_prefill_batch(self._h, arr, n, eptr, cnt, int(prefill_chunk) * n if prefill_chunk else 0, 1, stream_handle()), "lmx_prefill_batch")
+        self._prefill_packed([p["cache"].seqs[0] for p in prepared], [self._packed_rows(p["embeds"], p["valid"]) for p in prepared], prefill_chunk)
         return None
 
     def _prefill_request(self, ids, images, attention_mask, sampling, prefill_chunk: int = 0, return_logits: bool = False, stop=None):

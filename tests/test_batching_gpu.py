@@ -409,3 +409,18 @@ def test_packed_prefill_equals_per_request_prefill(cuda, name):
     # and a single request through generate() (its own lmx_prefill) is the same sequence as inside the packed batch
     one = model.generate(inputs=prompts[3][None], images=images[3], do_sample=False, max_new_tokens=7, eos_token_id=-1)
     assert torch.equal(one[0], ref[3])
+
+
+@pytest.mark.parametrize("name", ["tiny", "tiny_gqa"])
+def test_packed_prefill_of_one_request_equals_its_prefill_bf16(cuda, name):
+    """bf16: generate_batch with ONE request walks the same rows per GEMM packed (lmx_prefill_batch) as request by request (lmx_prefill, which may
+    fuse RoPE into the q|k|v GEMM — bit-identical, tests/test_qkv_fuse_gpu.py), whole or in pieces that cut the prompt: the ids are the same bits."""
+    from synthetic import build as harness, recipes as synth
+    cfg = synth.CONFIGS[name]
+    model = harness.build_model(cfg, dtype=torch.bfloat16, seed=0, weights=synth.make_weights(cfg, 0))
+    prompts = [torch.from_numpy(synth.make_prompt(cfg, 33, image_positions=(6,), seed=33)).to(cuda)]
+    images = [torch.from_numpy(synth.make_pixels(cfg, 1, seed=43)).to(cuda).to(torch.bfloat16)]
+    for chunk in (0, 16):
+        ref = model.generate_batch(prompts, images, max_new_tokens=7, eos_token_id=-1, prefill_chunk=chunk, packed_prefill=False)
+        got = model.generate_batch(prompts, images, max_new_tokens=7, eos_token_id=-1, prefill_chunk=chunk)
+        assert torch.equal(got[0], ref[0]), chunk
