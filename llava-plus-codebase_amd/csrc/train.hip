@@ -647,22 +647,29 @@ enum { kEwSwiglu = 0, kEwGelu = 1, kEwGeluBwd = 2, kEwAdd = 3 };
 // op 0: out = round(round(silu(a)) * b)      LlamaMLP: act_fn(gate_proj(x)) * up_proj(x), each op rounded to T
 // op 1: out = gelu_erf(a)                    nn.GELU() of the mlp2x_gelu projector (llava/model/multimodal_projector/builder.py:33-51)
 // op 2: out = b * gelu'(a)                   its autograd: 0.5 (1 + erf(a / sqrt2)) + a exp(-a^2 / 2) / sqrt(2 pi)
+// 0.5 (1 + erf(a / sqrt2)) is evaluated as 0.5 erfc(-a / sqrt2): for a < -3 the sum cancels against erff's rounding near -1 (bf16 results
+// hundreds of ulps off near a = -5); erfcf keeps it to a few fp32 ulps.
 // op 3: out = a + b                          residual / branch-gradient sum
 template <typename T, int OP>
 __global__ __launch_bounds__(256) void ew_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, size_t n) {
+#pragma clang fp contract(off)            // both forms round every operation where the source does (they must give the same bits)
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float x = to_f32(a[i]);
     float r;
     if (OP == kEwSwiglu) r = round_to<T>(x / (1.f + expf(-x))) * to_f32(b[i]);
-    else if (OP == kEwGelu) r = 0.5f * x * (1.f + erff(x * 0.70710678118654752f));
-    else if (OP == kEwGeluBwd) r = to_f32(b[i]) * (0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * expf(-0.5f * x * x) * 0.3989422804014327f);
+    else if (OP == kEwGelu) r = 0.5f * x * erfcf(-x * 0.70710678118654752f);
+    else if (OP == kEwGeluBwd) r = to_f32(b[i]) * (0.5f * erfcf(-x * 0.70710678118654752f) + x * expf(-0.5f * x * x) * 0.3989422804014327f);
     else r = x + to_f32(b[i]);
+    // hipcc fuses the last multiply with an fp16 conversion into one v_fma_mixlo_f16 (one rounding of the exact product; the pragma does not stop
+    // it), ew8_kernel's packed conversion rounds twice like torch's fp32 op + .to(half): keep r a rounded fp32 value, or the forms differ by an ulp.
+    asm volatile("" : "+v"(r));
     out[i] = from_f32<T>(r);
 }
 // the same arithmetic on 8 elements per lane (16-byte loads / stores of 16-bit tensors): the one-element form ran the residual adds of the backward at 1 TB/s
 template <typename T, int OP>
 __global__ __launch_bounds__(256) void ew8_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, size_t n8) {
+#pragma clang fp contract(off)            // as in ew_kernel
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n8) return;
     const uint4 av = reinterpret_cast<const uint4*>(a)[i];
@@ -678,8 +685,8 @@ __global__ __launch_bounds__(256) void ew8_kernel(const T* __restrict__ a, const
             const float x = hl ? unpack_hi<T>(aw[c]) : unpack_lo<T>(aw[c]);
             const float y = hl ? unpack_hi<T>(bw[c]) : unpack_lo<T>(bw[c]);
             if (OP == kEwSwiglu) r[hl] = round_to<T>(x / (1.f + expf(-x))) * y;
-            else if (OP == kEwGelu) r[hl] = 0.5f * x * (1.f + erff(x * 0.70710678118654752f));
-            else if (OP == kEwGeluBwd) r[hl] = y * (0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * expf(-0.5f * x * x) * 0.3989422804014327f);
+            else if (OP == kEwGelu) r[hl] = 0.5f * x * erfcf(-x * 0.70710678118654752f);
+            else if (OP == kEwGeluBwd) r[hl] = y * (0.5f * erfcf(-x * 0.70710678118654752f) + x * expf(-0.5f * x * x) * 0.3989422804014327f);
             else r[hl] = x + y;
         }
         ow[c] = pack2<T>(r[0], r[1]);

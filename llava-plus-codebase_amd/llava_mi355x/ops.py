@@ -333,19 +333,24 @@ def cast_f32(src, out):
     return out
 
 
-def col_sum(dy):
-    """fp32 column sums of dy [rows, cols] (bias gradient)."""
-    _need_cuda(dy)
-    out = torch.empty(dy.shape[1], dtype=torch.float32, device=dy.device)
+def col_sum(dy, out=None):
+    """fp32 column sums of dy [rows, cols] (bias gradient); dy may be a column window of a wider buffer."""
+    _need_cuda_rows(dy)
+    _need_cuda(out)
+    if out is None:
+        out = torch.empty(dy.shape[1], dtype=torch.float32, device=dy.device)
+    assert out.dtype == torch.float32 and out.numel() == dy.shape[1]
     check(lib.lmx_op_col_sum(torch_dtype_code(dy.dtype), ptr(dy), dy.stride(0), dy.shape[0], dy.shape[1], ptr(out), stream_handle()), "col_sum")
     return out
 
 
-def gather_embed(src, table, feats=None):
-    """Rows of `table` (src >= 0), zero rows (src == -1) and rows of `feats` (src == -2 - k) -> [len(src), H]."""
-    _need_cuda(src, table, feats)
+def gather_embed(src, table, feats=None, out=None):
+    """Rows of `table` (src >= 0), zero rows (src == -1) and rows of `feats` (src == -2 - k) -> [len(src), H] (into `out` when given)."""
+    _need_cuda(src, table, feats, out)
     assert src.dtype == torch.int32 and table.is_contiguous() and (feats is None or feats.is_contiguous())
-    out = torch.empty((src.numel(), table.shape[1]), dtype=table.dtype, device=table.device)
+    if out is None:
+        out = torch.empty((src.numel(), table.shape[1]), dtype=table.dtype, device=table.device)
+    assert out.shape == (src.numel(), table.shape[1]) and out.dtype == table.dtype
     check(lib.lmx_op_gather_embed(torch_dtype_code(table.dtype), ptr(src), ptr(table), ptr(feats), ptr(out), src.numel(), table.shape[1], stream_handle()),
           "gather_embed")
     return out

@@ -54,6 +54,25 @@ def test_gemm8p_small(cuda, dt, variant, M, N, K):
     assert_one_ulp(got, ref, dt, 2e-5 * float(ref.abs().max()), f"variant {variant} {M}x{N}x{K}")
 
 
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("M", [4352, 4416])
+def test_gemm8p_grouped_tile_order_ragged_last_group(cuda, dt, M):
+    """Variant 35 (un-split: S == 1, so gemm_tile_of's grouped order from 16 M-tiles on) at 17 / 18 M-tiles x 5 N-tiles: the last group of 4 M-tiles
+    holds 1 / 2 (the gm < GM branch) and the grid of 85 / 90 workgroups is not a multiple of the 8 XCDs.  Into a NaN-filled out=: within 1 ulp of the
+    once-rounded fp64 product, and bit-equal, block by block, to the same variant on row slices of at most 15 M-tiles (the column-major order).  A
+    tile's arithmetic does not depend on the order tiles run in, so a missing, doubled or misplaced tile cannot pass."""
+    from llava_mi355x import ops
+    N, K, rows = 1280, 512, 15 * 256
+    x, w = _mk(M, N, K, dt, cuda, M + 1)
+    out = torch.full((M, N), float("nan"), dtype=DT[dt], device=cuda)
+    ops.gemm(x, w, variant=35, out=out)
+    assert torch.isfinite(out.float()).all()
+    ref = x.double() @ w.double().t()
+    assert_one_ulp(out, ref, dt, 2e-5 * float(ref.abs().max()), f"variant 35 {M}x{N}x{K}")
+    for r0 in range(0, M, rows):
+        assert torch.equal(out[r0:r0 + rows], ops.gemm(x[r0:r0 + rows], w, variant=35)), f"rows {r0}.."
+
+
 def test_gemm8p_transpose_detecting(cuda):
     from llava_mi355x import ops
     M = N = 256; K = 128

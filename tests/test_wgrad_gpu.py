@@ -40,6 +40,9 @@ SHAPES = [
     (1024, 768, 256),        # q|k|v of the tiny geometry
     (2048, 1024, 768),       # 12 tiles
     (512, 4096, 4352),       # 272 tiles: more workgroups than CUs, the XCD remap's ragged end
+    (512, 11008, 256),       # 43 M-tiles (7B gate / up): gemm_tile_of's ragged last group (43 % 4 = 3), 43 workgroups (43 & 7 = 3)
+    (256, 13824, 256),       # 54 M-tiles (13B gate / up): a last group of 2
+    (128, 22016, 512),       # 86 M-tiles: the fused gate | up width of the 7B geometry
     (4096, 12288, 4096),     # q|k|v of the 7B geometry, two samples' rows
     (2048, 4096, 11008),     # down_proj of the 7B geometry, one sample's rows
 ]
