@@ -165,6 +165,11 @@ enum Act : int { kActNone = 0, kActQuickGelu = 1, kActGeluErf = 2, kActSiluMul =
 
 __device__ __forceinline__ float act_quick_gelu(float x) { return x / (1.f + __expf(-1.702f * x)); }
 __device__ __forceinline__ float act_gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
+// The same function as 0.5 x erfc(-x / sqrt2).  For x < -1 the sum 1 + erff above cancels against erff's rounding near -1: its absolute error stays near
+// |x| 2^-25, but relative to the result it grows from 2^-18 at x = -2 to 2^-14 at x = -3 and to 1 near x = -5.5.  The MFMA GEMM epilogues keep the form above (their
+// outputs are 16-bit, their checks absolute, and the flagship prefill must keep its bits); the kernels that are held to a RELATIVE bound of a few fp32 ulps per
+// output (the decode GEMV family and the fp32 verification GEMM) take this one.
+__device__ __forceinline__ float act_gelu_erfc(float x) { return 0.5f * x * erfcf(-x * 0.70710678118654752f); }
 __device__ __forceinline__ float act_silu(float x) { return x / (1.f + __expf(-x)); }
 
 // ---- XCD-aware block remap (8 XCDs, block b is dispatched to XCD b % 8). Bijective for any nwg.

@@ -319,6 +319,8 @@ __global__ __launch_bounds__(256) void gather_token_kernel(const int64_t* __rest
 }
 
 void launch_gather_token(int dtype, const int64_t* tok_ptr, const void* table, void* out, int H, int vocab, hipStream_t st) {
+    // the kernel copies the row in 16-byte pieces and clamps the id into [0, vocab): a width off that grid would lose its tail, an empty vocabulary would read row -1
+    LMX_REQUIRE(H > 0 && H % 8 == 0 && vocab > 0, "gather_token: hidden size must be a positive multiple of 8 and the vocabulary non-empty");
 #define L(TT) hipLaunchKernelGGL(gather_token_kernel<TT>, dim3(2), dim3(256), 0, st, tok_ptr, (const TT*)table, (TT*)out, H, vocab)
     if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
 #undef L

@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs a) {
                 acc[i][j] = v;
                 continue;
             }
-            v = apply_act(v, act);
+            v = apply_act_rel(v, act);
             if (R) v += R[(size_t)m * a.ldr + n];
             C[(size_t)m * a.ldc + n] = v;
         }
@@ -611,7 +611,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
         for (int mb = 0; mb < MB; ++mb) {
             float v = acc[r][mb];
             if (bias) v += to_f32(bias[n]);
-            v = apply_act(v, a.act);
+            v = apply_act_rel(v, a.act);
             if (Rr) v += to_f32(Rr[(size_t)mb * a.ldr + n]);
             C[(size_t)mb * a.ldc + n] = from_f32<T>(v);
         }
@@ -780,7 +780,8 @@ static void launch_gemv2_r(const GemvArgs& a, hipStream_t st) {
     else launch_gemv2_rx<T, R, P, 8>(a, st);
 }
 
-// does the single-row linear of this shape take the hand-counted stream (gemv2_body)?  16-byte rows, 32-bit row offsets, K <= 16384, an aligned x row
+// does the single-row linear of this shape take the hand-counted stream (gemv2_body)?  16-byte rows, 32-bit row offsets, K <= 16384, an aligned x row.  (launch_gemv
+// has checked the alignment before it asks; decode_attn.hip asks on its own, so the tests stay.)
 bool gemv2_applies(int dtype, const GemvArgs& a) {
     if (dtype != kBF16 && dtype != kF16) return false;
     if (((size_t)a.ldw * 2) % 16 != 0 || (size_t)a.N * a.ldw * 2 >= ((size_t)1 << 32)) return false;
@@ -832,6 +833,13 @@ void launch_gemv(int dtype, const GemvArgs& a, int MB, hipStream_t st) {
     LMX_REQUIRE(a.K % 8 == 0, "gemv: K must be a multiple of 8");
     LMX_REQUIRE((size_t)MB * a.K * dtype_size(dtype) + 16 <= 160 * 1024, "gemv: x does not fit LDS");
     if (a.act == kActSiluMul) LMX_REQUIRE(a.N % 64 == 0, "gemv: SiLU·mul needs N % 64 == 0");
+    if (a.act == kActSiluMul) LMX_REQUIRE(a.R == nullptr, "gemv: the SiLU·mul epilogue adds no residual");
+    // every lane reads x, the norm weights and the weight rows in 16-byte pieces
+    const size_t es = dtype_size(dtype);
+    LMX_REQUIRE(a.N > 0 && a.K > 0 && MB >= 1 && MB <= 4, "gemv: empty problem or batch rows outside 1..4");
+    LMX_REQUIRE(a.ldw >= a.K && ((size_t)a.ldw * es) % 16 == 0 && reinterpret_cast<uintptr_t>(a.W) % 16 == 0, "gemv: weight rows must be 16-byte aligned");
+    LMX_REQUIRE(MB == 1 || (a.ldx >= a.K && ((size_t)a.ldx * es) % 16 == 0), "gemv: x rows must be 16-byte aligned");
+    LMX_REQUIRE(reinterpret_cast<uintptr_t>(a.X) % 16 == 0 && reinterpret_cast<uintptr_t>(a.norm_w) % 16 == 0, "gemv: x and the norm weights must be 16-byte aligned");
     if (dtype == kBF16) launch_gemv_t<bf16_t>(a, MB, st);
     else if (dtype == kF16) launch_gemv_t<f16_t>(a, MB, st);
     else if (dtype == kF32) launch_gemv_t<float>(a, MB, st);

@@ -29,6 +29,12 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == kActGeluErf) return act_gelu_erf(v);
     return v;
 }
+// the fp32-output-accurate form: GELU-erf through erfc (common.h), for the GEMV family and the fp32 GEMM
+__device__ __forceinline__ float apply_act_rel(float v, int act) {
+    if (act == kActQuickGelu) return act_quick_gelu(v);
+    if (act == kActGeluErf) return act_gelu_erfc(v);
+    return v;
+}
 
 template <typename T> __device__ __forceinline__ void store4(T* p, const float (&v)[4]);
 template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, const float (&v)[4]) {

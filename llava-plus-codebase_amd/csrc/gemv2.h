@@ -174,7 +174,7 @@ __device__ __forceinline__ void gemv2_body(const GemvArgs& a, int bid, char* sme
         if (n >= a.N) continue;
         float v = acc[r];
         if (bias) v += to_f32(bias[n]);
-        v = apply_act(v, a.act);
+        v = apply_act_rel(v, a.act);
         if (Rr) v += rres[r];
         if constexpr (PUBLISH) {
             // hand-over inside the launch (decode_attn.hip): one naturally aligned 8-byte {value bits, tag} granule per output, ONE relaxed agent-scope store

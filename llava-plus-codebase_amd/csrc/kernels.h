@@ -58,13 +58,15 @@ struct GemvArgs {
     const void* W;        // [N, K]
     void* C;              // [MB, N] (or N/2 for SiLU·mul)
     const void* bias;     // [N] or null
-    const void* R;        // residual [MB, N] or null; may alias C
+    const void* R;        // residual [MB, N] or null, added after the activation; may alias C.  Must be null with kActSiluMul (that epilogue adds none)
     const void* norm_w;   // if non-null: x := RMSNorm(x) * norm_w, fused into the x staging
     float eps;
     int N, K;
     int ldx, ldw, ldc, ldr;
     int act;
 };
+// Preconditions (checked): MB in 1..4, K % 8 == 0, MB rows of x fit LDS; X, W and norm_w 16-byte aligned, weight rows (ldw) and, for MB > 1, x rows (ldx) multiples
+// of 16 bytes (every lane reads 16 bytes at a time); N % 64 == 0 and R == null with kActSiluMul.  C, R and bias need element alignment only.
 void launch_gemv(int dtype, const GemvArgs& a, int MB, hipStream_t st);
 // does launch_gemv(MB = 1) of this shape take the hand-counted weight stream (gemv2.h)?
 bool gemv2_applies(int dtype, const GemvArgs& a);

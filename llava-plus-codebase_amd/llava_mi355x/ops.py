@@ -42,13 +42,17 @@ def gemm(x, w, bias=None, residual=None, act=_C.ACT_NONE, variant=0, out=None):
 
 
 def gemv(x, w, bias=None, residual=None, norm_w=None, eps=1e-5, act=_C.ACT_NONE, out=None):
-    """Decode-time linear for 1..4 rows: act(norm(x) @ w.T + bias) (+ residual)."""
-    _need_cuda(x, w, bias, residual, norm_w)
+    """Decode-time linear for 1..4 rows: act(norm(x) @ w.T + bias) (+ residual).  x, w, residual and out may be column windows of wider buffers (contiguous
+    rows, free row stride)."""
+    _need_cuda(bias, norm_w)
+    _need_cuda_rows(x, w, residual, out)
     MB, K = x.shape
     N = w.shape[0]
     n_out = N // 2 if act == _C.ACT_SILU_MUL else N
     if out is None:
         out = torch.empty((MB, n_out), dtype=x.dtype, device=x.device)
+    if w.shape[1] != K or tuple(out.shape) != (MB, n_out) or (residual is not None and tuple(residual.shape) != (MB, n_out)):
+        raise ValueError("gemv: x [MB, K], w [N, K], residual / out [MB, N] (N / 2 for SiLU*mul)")
     check(lib.lmx_op_gemv(torch_dtype_code(x.dtype), ptr(x), ptr(w), ptr(out), ptr(bias), ptr(residual), ptr(norm_w), eps,
                           MB, N, K, x.stride(0), w.stride(0), out.stride(0), residual.stride(0) if residual is not None else 0,
                           act, stream_handle()), "gemv")

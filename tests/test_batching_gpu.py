@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import linear_ref as L
 from golden_util import case_inputs, load
 
 pytestmark = pytest.mark.gpu
@@ -34,6 +35,7 @@ def test_skinny_gemm_plain(cuda, dt, M, N, K):
     got = ops.gemm(x, w, variant=SKINNY)
     ref = x.float() @ w.float().t()
     assert _rel_err(got, ref) < 1e-2
+    L.gemm16_check(got, x.double() @ w.double().t(), dt, False, f"skinny {M}x{N}x{K} {dt}")
     # same kernel reading the fragment-order copy of w (what the engine's decode batch uses): identical bits
     got_sw = ops.gemm(x, w, variant=SKINNY + 1)
     assert torch.equal(got, got_sw)
@@ -63,9 +65,11 @@ def test_skinny_gemm_bias_act_residual(cuda, M, act):
     ref = (pre if act == 0 else pre * torch.sigmoid(1.702 * pre) if act == 1 else torch.nn.functional.gelu(pre)) + r.float()
     got = ops.gemm(x, w, bias=b, residual=r, act=act, variant=SKINNY)
     assert _rel_err(got, ref) < 1e-2
+    L.gemm16_check(got, L.act64(x.double() @ w.double().t() + b.double(), act)[0] + r.double(), "bf16", act != 0, f"skinny act {act} M={M}")
     r2 = r.clone()
     ops.gemm(x, w, bias=b, residual=r2, act=act, out=r2, variant=SKINNY)      # C aliases R (the residual stream)
     assert _rel_err(r2, ref) < 1e-2
+    assert torch.equal(r2, got)
 
 
 @pytest.mark.parametrize("M,I", [(1, 352), (7, 352), (16, 352), (32, 352), (20, 8192), (32, 11008)])
@@ -79,6 +83,7 @@ def test_skinny_gemm_silu_mul(cuda, M, I):
     ref = torch.nn.functional.silu(x.float() @ g.float().t()) * (x.float() @ u.float().t())
     got = ops.gemm(x, fused, act=_C.ACT_SILU_MUL, variant=SKINNY)
     assert got.shape == (M, I) and _rel_err(got, ref) < 1e-2
+    L.gemm16_check(got, L.act64(x.double() @ g.double().t(), _C.ACT_SILU_MUL)[0] * (x.double() @ u.double().t()), "bf16", True, f"skinny SiLU*mul M={M} I={I}")
     assert torch.equal(got, ops.gemm(x, fused, act=_C.ACT_SILU_MUL, variant=SKINNY + 1))
 
 

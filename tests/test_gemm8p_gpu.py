@@ -11,8 +11,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-DT = {"bf16": torch.bfloat16, "f16": torch.float16}
-MANT = {"bf16": 8, "f16": 11}          # significand bits incl. the hidden one
+DT = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
+MANT = {"bf16": 8, "f16": 11, "f32": 24}          # significand bits incl. the hidden one
 
 
 def ulp_of(ref64: torch.Tensor, dt: str) -> torch.Tensor:

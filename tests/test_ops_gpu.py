@@ -6,11 +6,29 @@ import math
 import pytest
 import torch
 
+import linear_ref as L
+
 pytestmark = pytest.mark.gpu
 
 DT = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
-# relative-to-magnitude tolerances per storage dtype (fp32 accumulate everywhere)
+# relative-to-magnitude tolerances per storage dtype (fp32 accumulate everywhere).  The linears are ALSO held, element by element, to the float64 statements of
+# linear_ref.py: one ulp of the once-rounded float64 result for the 16-bit GEMMs, ulp_T(ref) + the derived fp32 bound for the fp32 GEMM and the GEMV family.
 TOL = {"bf16": 1.2e-2, "f16": 2e-3, "f32": 2e-5}
+
+
+def _gemm_check(got, x, w, dt, what, bias=None, residual=None, act=0):
+    """Per-element check of one GEMM output (w: the [N, K] weight, or the (gate, up) pair for SiLU*mul)."""
+    if dt == "f32":                                             # gemm_f32_kernel: one fmaf chain of K terms per output, no tree
+        ref, E, _ = L.linear_ref(x, w, dt, bias=bias, residual=residual, act=act, chain=x.shape[1], tree=0)
+        L.check(got, ref, E, dt, what)
+        return
+    if act == L.ACT_SILU_MUL:
+        ref = L.act64(x.double() @ w[0].double().t(), act)[0] * (x.double() @ w[1].double().t())
+    else:
+        y = x.double() @ w.double().t()
+        ref = L.act64(y + bias.double() if bias is not None else y, act)[0]
+        ref = ref + residual.double() if residual is not None else ref
+    L.gemm16_check(got, ref, dt, act != 0, what)
 
 
 def _rel_err(got, ref):
@@ -39,6 +57,7 @@ def test_gemm_plain(cuda, dt, variant, M, N, K):
     got = ops.gemm(x, w, variant=variant)
     ref = x.float() @ w.float().t()
     assert _rel_err(got, ref) < TOL[dt]
+    _gemm_check(got, x, w, dt, f"variant {variant} {M}x{N}x{K} {dt}")
 
 
 def test_gemm_is_transpose_detecting(cuda):
@@ -63,10 +82,12 @@ def test_gemm_bias_act_residual(cuda, dt, act):
     got = ops.gemm(x, w, bias=b, residual=r, act=act)
     ref = _act_ref(x.float() @ w.float().t() + b.float(), act) + r.float()
     assert _rel_err(got, ref) < TOL[dt]
+    _gemm_check(got, x, w, dt, f"act {act} {dt}", bias=b, residual=r, act=act)
     # in-place residual (C aliases R), the way the engine keeps the residual stream
     r2 = r.clone()
     ops.gemm(x, w, bias=b, residual=r2, act=act, out=r2)
     assert _rel_err(r2, ref) < TOL[dt]
+    assert torch.equal(r2, got)
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16", "f32"])
@@ -83,9 +104,11 @@ def test_gemm_silu_mul(cuda, dt, M):
         got = ops.gemm(x, fused, act=_C.ACT_SILU_MUL, variant=variant)
         assert got.shape == (M, I)
         assert _rel_err(got, ref) < TOL[dt], f"variant {variant}"
+        _gemm_check(got, x, (g, u), dt, f"SiLU*mul variant {variant} M={M} {dt}", act=_C.ACT_SILU_MUL)
     if M <= 4:
         got2 = ops.gemv(x, fused, act=_C.ACT_SILU_MUL)
         assert _rel_err(got2, ref) < TOL[dt]
+        L.check(got2, *L.linear_ref(x, (g, u), dt, act=_C.ACT_SILU_MUL)[:2], dt, f"gemv SiLU*mul {dt}")
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16", "f32"])
@@ -98,6 +121,7 @@ def test_gemv(cuda, dt, MB, N, K):
     got = ops.gemv(x, w, bias=b, residual=r)
     ref = x.float() @ w.float().t() + b.float() + r.float()
     assert _rel_err(got, ref) < TOL[dt]
+    L.check(got, *L.linear_ref(x, w, dt, bias=b, residual=r)[:2], dt, f"gemv bias + residual {dt}")
     # fused RMSNorm prologue
     g = (1 + 0.1 * torch.randn(K, device=cuda)).to(DT[dt])
     got = ops.gemv(x, w, norm_w=g, eps=1e-5)
@@ -105,6 +129,14 @@ def test_gemv(cuda, dt, MB, N, K):
     xn = (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + 1e-5)).to(DT[dt]).float() * g.float()
     ref = xn.to(DT[dt]).float() @ w.float().t()
     assert _rel_err(got, ref) < TOL[dt]
+    _gemv_norm_check(got, x, w, dt, g, f"gemv norm {dt}")
+
+
+def _gemv_norm_check(got, x, w, dt, g, what, act=0):
+    """Per-element check of a GEMV with the RMSNorm prologue; the flippable set of these (device-drawn) inputs must stay under linear_ref's cap."""
+    ref, E, frac = L.linear_ref(x, w, dt, norm_w=g, eps=1e-5, act=act)
+    assert frac <= L.FLIP_MAX_FRACTION, f"{what}: flippable fraction {frac:.4f}"
+    L.check(got, ref, E, dt, what)
 
 
 # the decode linears of LLaVA-1.5-7B / 13B at their REAL shapes, each with the epilogue / prologue the decode step fuses into it (VERDICT r3 item 5):
@@ -126,10 +158,12 @@ def test_gemv2_real_decode_shapes(cuda, dt, H, I, nh):
     wqkv = W(3 * H, H)
     got = ops.gemv(h, wqkv, norm_w=g1, eps=1e-5)
     assert _rel_err(got, rms(h, g1) @ wqkv.float().t()) < TOL[dt]
+    _gemv_norm_check(got, h, wqkv, dt, g1, "q|k|v")
     # o_proj: [H, H] + residual
     a = torch.randn(1, H, device=cuda).to(T); wo = W(H, H)
     got = ops.gemv(a, wo, residual=h)
     assert _rel_err(got, a.float() @ wo.float().t() + h.float()) < TOL[dt]
+    L.check(got, *L.linear_ref(a, wo, dt, residual=h)[:2], dt, "o_proj + residual")
     # in place on the residual stream, as the engine runs it
     h2 = h.clone(); ops.gemv(a, wo, residual=h2, out=h2)
     assert torch.equal(h2, got)
@@ -140,14 +174,17 @@ def test_gemv2_real_decode_shapes(cuda, dt, H, I, nh):
     xn = rms(h, g1)
     ref = torch.nn.functional.silu(xn @ wg.float().t()) * (xn @ wu.float().t())
     assert got.shape == (1, I) and _rel_err(got, ref) < TOL[dt]
+    _gemv_norm_check(got, h, (wg, wu), dt, g1, "gate|up SiLU*mul", act=_C.ACT_SILU_MUL)
     # down_proj: [H, I] + residual
     act = torch.randn(1, I, device=cuda).to(T); wd = W(H, I)
     got = ops.gemv(act, wd, residual=h)
     assert _rel_err(got, act.float() @ wd.float().t() + h.float()) < TOL[dt]
+    L.check(got, *L.linear_ref(act, wd, dt, residual=h)[:2], dt, "down_proj + residual")
     # lm_head: [32000, H] with the final norm
     wl = W(32000, H)
     got = ops.gemv(h, wl, norm_w=g1, eps=1e-5)
     assert _rel_err(got, rms(h, g1) @ wl.float().t()) < TOL[dt]
+    _gemv_norm_check(got, h, wl, dt, g1, "lm_head")
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16", "f32"])
