@@ -243,6 +243,8 @@ int lmx_profile_read(lmx_model* m, char* names_buf, int32_t names_cap, double* m
 int lmx_model_set_option(lmx_model* m, const char* key, int32_t value);
 
 /* ---- single-op entry points (unit parity tests + microbenchmarks; same kernels the engine launches) --------------- */
+/* Every lmx_op_* that takes a dtype returns non-zero with a message (lmx_last_error) for a code outside LMX_DTYPE_* 0..2, or outside 1..2 for the entries that
+ * exist for the 16-bit types only; no kernel is launched and no buffer is touched. */
 int lmx_op_gemm(int32_t dtype, const void* x, const void* w, void* c, const void* bias, const void* residual,
                 int32_t M, int32_t N, int32_t K, int32_t ldx, int32_t ldw, int32_t ldc, int32_t ldr, int32_t act, int32_t variant, void* stream);
 int lmx_op_gemv(int32_t dtype, const void* x, const void* w, void* c, const void* bias, const void* residual, const void* norm_w, float eps,

@@ -15,6 +15,7 @@
 //   (HBM-bound KV streaming) and as the fp32 verification-mode attention for whole prompts.
 #include <cstdlib>
 #include "common.h"
+#include "dispatch.h"
 #include "kernels.h"
 #include "attention_decode.h"
 #include "attention_mfma.h"
@@ -312,37 +313,32 @@ __global__ __launch_bounds__(512) void flash_prefill2_kernel(FlashArgs a) {
     }
 }
 
+// two key groups per query block (flash_prefill2_kernel): 8 waves, ring of 2 (D = 128) / 3 (D = 64) rounds of two tiles
+template <typename T, int D, bool CAUSAL>
+static void launch_flash_prefill_t(const dim3& grid, const FlashArgs& a, hipStream_t st) {
+    const int smem2 = (D == 128 ? 2 : 3) * 2 * (FA_KT * D * 2 + D * FA_KT * 2);
+    auto kern = flash_prefill2_kernel<T, D, CAUSAL>;
+    static bool attr_set = false;
+    if (!attr_set) {
+        LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem2));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(512), smem2, st, a);
+}
+
 void launch_flash_prefill(int dtype, int D, const FlashArgs& a, hipStream_t st) {
-    LMX_REQUIRE(dtype == kBF16 || dtype == kF16, "flash prefill is the 16-bit path (fp32 verification uses decode_attn)");
     LMX_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128");
     LMX_REQUIRE(a.s_max % 64 == 0, "KV cache length must be a multiple of 64");
     LMX_REQUIRE(a.kv_len <= a.s_max && a.q_len > 0, "bad lengths");
     LMX_REQUIRE(a.q_stride % 8 == 0 && a.o_stride % 4 == 0, "q/o strides must keep 16-byte alignment");
     const dim3 grid(cdiv(a.q_len, FA_QB) * a.n_heads, 1, 1);
-    {
-        // two key groups per query block (flash_prefill2_kernel): 8 waves, ring of 2 (D = 128) / 3 (D = 64) rounds of two tiles
-        const int smem2 = (D == 128 ? 2 : 3) * 2 * (FA_KT * D * 2 + D * FA_KT * 2);
-#define LMX_FA2_LAUNCH(TT, DD, CC)                                                                                  \
-    do {                                                                                                            \
-        auto kern = flash_prefill2_kernel<TT, DD, CC>;                                                              \
-        static bool attr_set = false;                                                                               \
-        if (!attr_set) {                                                                                            \
-            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem2)); \
-            attr_set = true;                                                                                        \
-        }                                                                                                           \
-        hipLaunchKernelGGL(kern, grid, dim3(512), smem2, st, a);                                                    \
-    } while (0)
-        if (dtype == kBF16) {
-            if (D == 128) { if (a.causal) LMX_FA2_LAUNCH(bf16_t, 128, true); else LMX_FA2_LAUNCH(bf16_t, 128, false); }
-            else          { if (a.causal) LMX_FA2_LAUNCH(bf16_t, 64, true);  else LMX_FA2_LAUNCH(bf16_t, 64, false); }
-        } else {
-            if (D == 128) { if (a.causal) LMX_FA2_LAUNCH(f16_t, 128, true); else LMX_FA2_LAUNCH(f16_t, 128, false); }
-            else          { if (a.causal) LMX_FA2_LAUNCH(f16_t, 64, true);  else LMX_FA2_LAUNCH(f16_t, 64, false); }
-        }
-#undef LMX_FA2_LAUNCH
-        LMX_CHECK_HIP(hipGetLastError());
-        return;
-    }
+    dispatch_dtype16(dtype, "flash_prefill", [&](auto t) {      // (fp32 verification uses decode_attn)
+        dispatch_head_dim(D, "flash_prefill", [&](auto d) {
+            constexpr int DD = decltype(d)::value;
+            if (a.causal) launch_flash_prefill_t<LMX_T(t), DD, true>(grid, a, st); else launch_flash_prefill_t<LMX_T(t), DD, false>(grid, a, st);
+        });
+    });
+    LMX_CHECK_HIP(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -486,13 +482,9 @@ void launch_decode_attn(int dtype, int D, const DecodeAttnArgs& a, hipStream_t s
     LMX_REQUIRE(a.s_max % 64 == 0, "KV cache length must be a multiple of 64");
     LMX_REQUIRE(a.n_split >= 1 && a.ws != nullptr, "decode attention needs a workspace");
     LMX_REQUIRE((size_t)(a.causal ? a.s_max : a.kv_total + 64) * 4 + 64 <= 160 * 1024, "score row does not fit LDS");
-#define LMX_DA(TT)                                                                                     \
-    do { if (D == 128) launch_decode_attn_t<TT, 128>(a, st); else launch_decode_attn_t<TT, 64>(a, st); } while (0)
-    if (dtype == kBF16) LMX_DA(bf16_t);
-    else if (dtype == kF16) LMX_DA(f16_t);
-    else if (dtype == kF32) LMX_DA(float);
-    else throw Error{"decode_attn: bad dtype"};
-#undef LMX_DA
+    dispatch_dtype(dtype, "decode_attn", [&](auto t) {
+        dispatch_head_dim(D, "decode_attn", [&](auto d) { launch_decode_attn_t<LMX_T(t), decltype(d)::value>(a, st); });
+    });
 }
 
 }  // namespace lmx
@@ -521,16 +513,15 @@ void launch_decode_fused(int dtype, int D, const DecodeFusedArgs& a, hipStream_t
     if (a.tab && D == 128 && (dtype == kBF16 || dtype == kF16) && a.s_max % BA_PIECE == 0) {
         // the decode batch of 16-bit models with head_dim 128 (attention_batch.h): one workgroup per (sequence, head), waves stream the keys — 44.8 -> 38.9 us per
         // layer at 8 sequences, 143 -> 134 at 32 against the chunked launch below (profiles/r05_batch_attn_wave.jsonl)
-        if (dtype == kBF16) launch_decode_attn_wave_t<bf16_t>(a, st); else launch_decode_attn_wave_t<f16_t>(a, st);
+        dispatch_dtype16(dtype, "decode_fused", [&](auto t) { launch_decode_attn_wave_t<LMX_T(t)>(a, st); });
         LMX_CHECK_HIP(hipGetLastError());
         return;
     }
-#define LMX_DF(TT, DD) hipLaunchKernelGGL((decode_fused_kernel<TT, DD>), dim3(a.n_heads, a.n_split, a.tab ? a.n_seq : 1), dim3(256), 0, st, a)
-    if (dtype == kBF16) { if (D == 128) LMX_DF(bf16_t, 128); else LMX_DF(bf16_t, 64); }
-    else if (dtype == kF16) { if (D == 128) LMX_DF(f16_t, 128); else LMX_DF(f16_t, 64); }
-    else if (dtype == kF32) { if (D == 128) LMX_DF(float, 128); else LMX_DF(float, 64); }
-    else throw Error{"decode_fused: bad dtype"};
-#undef LMX_DF
+    dispatch_dtype(dtype, "decode_fused", [&](auto t) {
+        dispatch_head_dim(D, "decode_fused", [&](auto d) {
+            hipLaunchKernelGGL((decode_fused_kernel<LMX_T(t), decltype(d)::value>), dim3(a.n_heads, a.n_split, a.tab ? a.n_seq : 1), dim3(256), 0, st, a);
+        });
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -582,12 +573,9 @@ void launch_attn_probs(int dtype, int D, const AttnProbsArgs& a, hipStream_t st)
     LMX_REQUIRE(a.n_kv_heads >= 1 && a.n_heads % a.n_kv_heads == 0, "attn_probs: heads must be a multiple of kv heads");
     const size_t smem = ((size_t)a.kv_total + 8) * sizeof(float);
     LMX_REQUIRE(smem <= 64 * 1024, "attn_probs: score row does not fit LDS");
-#define LMX_AP(TT, DD) hipLaunchKernelGGL((attn_probs_kernel<TT, DD>), dim3(a.n_rows, a.n_heads), dim3(256), smem, st, a)
-    if (dtype == kBF16) { if (D == 128) LMX_AP(bf16_t, 128); else LMX_AP(bf16_t, 64); }
-    else if (dtype == kF16) { if (D == 128) LMX_AP(f16_t, 128); else LMX_AP(f16_t, 64); }
-    else if (dtype == kF32) { if (D == 128) LMX_AP(float, 128); else LMX_AP(float, 64); }
-    else throw Error{"attn_probs: bad dtype"};
-#undef LMX_AP
+    dispatch_dtype(dtype, "attn_probs", [&](auto t) {
+        dispatch_head_dim(D, "attn_probs", [&](auto d) { hipLaunchKernelGGL((attn_probs_kernel<LMX_T(t), decltype(d)::value>), dim3(a.n_rows, a.n_heads), dim3(256), smem, st, a); });
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 

@@ -32,6 +32,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "dispatch.h"
 #include "kernels.h"
 #include "engine.h"
 #include "attention_mfma.h"
@@ -448,28 +449,29 @@ void launch_attn_bwd_mfma(int dtype, int D, const void* q, const void* k, const 
               have ? 1 : 0};
     if (have) {
         const unsigned g = (unsigned)(((long)Tp * heads + 3) / 4);
-        if (dtype == kBF16) { if (D == 128) hipLaunchKernelGGL((attn_delta_kernel<bf16_t, 128>), dim3(g), dim3(256), 0, st, (const bf16_t*)dO, (const bf16_t*)out, delta, Tn, Tp, heads, ldo, ldout);
-                              else hipLaunchKernelGGL((attn_delta_kernel<bf16_t, 64>), dim3(g), dim3(256), 0, st, (const bf16_t*)dO, (const bf16_t*)out, delta, Tn, Tp, heads, ldo, ldout); }
-        else { if (D == 128) hipLaunchKernelGGL((attn_delta_kernel<f16_t, 128>), dim3(g), dim3(256), 0, st, (const f16_t*)dO, (const f16_t*)out, delta, Tn, Tp, heads, ldo, ldout);
-               else hipLaunchKernelGGL((attn_delta_kernel<f16_t, 64>), dim3(g), dim3(256), 0, st, (const f16_t*)dO, (const f16_t*)out, delta, Tn, Tp, heads, ldo, ldout); }
+        dispatch_dtype16(dtype, "attn_bwd_mfma", [&](auto t) {
+            dispatch_head_dim(D, "attn_bwd_mfma", [&](auto d) {
+                hipLaunchKernelGGL((attn_delta_kernel<LMX_T(t), decltype(d)::value>), dim3(g), dim3(256), 0, st, (const LMX_T(t)*)dO, (const LMX_T(t)*)out, delta, Tn, Tp, heads, ldo, ldout);
+            });
+        });
     }
     const int nblk = (Tn + 127) / 128;
     const int rt = 64 * D * 2;
     const int smem_dq = 2 * 2 * rt, smem_dkv = 2 * (2 * rt + 512);          // two ring slots each: 64 / 66.5 KiB at D = 128 -> two workgroups per CU
-#define LB(TT, DD)                                                                                                                              \
-    do {                                                                                                                                       \
-        static bool attr = false;                                                                                                              \
-        if (!attr) {                                                                                                                           \
-            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_mfma_kernel<TT, DD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));  \
-            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_mfma_kernel<TT, DD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            attr = true;                                                                                                                       \
-        }                                                                                                                                      \
-        hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<TT, DD>), dim3(nblk * heads), dim3(256), smem_dq, st, a);                                  \
-        hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<TT, DD>), dim3(nblk * kv_heads), dim3(256), smem_dkv, st, a);                             \
-    } while (0)
-    if (dtype == kBF16) { if (D == 128) LB(bf16_t, 128); else LB(bf16_t, 64); }
-    else { if (D == 128) LB(f16_t, 128); else LB(f16_t, 64); }
-#undef LB
+    dispatch_dtype16(dtype, "attn_bwd_mfma", [&](auto t) {
+        using T = LMX_T(t);
+        dispatch_head_dim(D, "attn_bwd_mfma", [&](auto d) {
+            constexpr int DD = decltype(d)::value;
+            static bool attr = false;               // one per (T, DD): every instantiation of this lambda body has its own
+            if (!attr) {
+                LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_mfma_kernel<T, DD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_mfma_kernel<T, DD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                attr = true;
+            }
+            hipLaunchKernelGGL((attn_bwd_dq_mfma_kernel<T, DD>), dim3(nblk * heads), dim3(256), smem_dq, st, a);
+            hipLaunchKernelGGL((attn_bwd_dkv_mfma_kernel<T, DD>), dim3(nblk * kv_heads), dim3(256), smem_dkv, st, a);
+        });
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 

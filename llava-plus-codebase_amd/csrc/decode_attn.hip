@@ -22,6 +22,7 @@
 // head, r4-F; tagged-granule merge, r3-D) — built, bit-identical, measured slower or equal, removed in round 5; profiles/EXPERIMENTS.md names the commits.
 #include "attention_decode.h"
 #include "common.h"
+#include "dispatch.h"
 #include "gemv2.h"
 #include "kernels.h"
 
@@ -297,8 +298,7 @@ __global__ __launch_bounds__(256) void decode_kv_attn_kernel(DecAttnArgs a, Gemv
     else gemv2_body<T, 2, 4, NX, true>(g, (int)blockIdx.x - n_attn, smem, a.kv_gran, a.pub_tag ? a.pub_tag : a.tag, a.ts);
 }
 
-void check_dec_attn(int dtype, int D, const DecAttnArgs& a, const char* who) {
-    LMX_REQUIRE(dtype == kBF16 || dtype == kF16, std::string(who) + ": 16-bit dtypes only");
+void check_dec_attn(int D, const DecAttnArgs& a, const char* who) {      // (the dtype: the launcher's dispatch_dtype16, which runs first)
     LMX_REQUIRE(D == 64 || D == 128, std::string(who) + ": head_dim must be 64 or 128");
     LMX_REQUIRE(a.pos >= 0 && a.pos < a.s_max && a.nkv >= 1 && a.nh % a.nkv == 0, std::string(who) + ": 0 <= pos < s_max, heads a multiple of kv heads");
     LMX_REQUIRE(a.n_split >= 1 && a.n_split <= DF_MAX_SPLIT && a.n_split * DF_CHUNK > a.pos && (a.n_split - 1) * DF_CHUNK <= a.pos && a.n_split * DF_CHUNK <= a.s_max,
@@ -308,12 +308,13 @@ void check_dec_attn(int dtype, int D, const DecAttnArgs& a, const char* who) {
 }  // namespace
 
 void launch_decode_attn_step(int dtype, int D, const DecAttnArgs& a, hipStream_t st) {
-    check_dec_attn(dtype, D, a, "decode_attn_step");
-    const size_t smem = dec_attn_smem_bytes(D);
-#define LA(TT, DD) LMX_LAUNCH((decode_attn_step_kernel<TT, DD>), dim3((unsigned)(a.nh * a.n_split)), dim3(256), smem, st, a)
-    if (dtype == kBF16) { if (D == 128) LA(bf16_t, 128); else LA(bf16_t, 64); }
-    else { if (D == 128) LA(f16_t, 128); else LA(f16_t, 64); }
-#undef LA
+    dispatch_dtype16(dtype, "decode_attn_step", [&](auto t) {
+        check_dec_attn(D, a, "decode_attn_step");
+        const size_t smem = dec_attn_smem_bytes(D);
+        dispatch_head_dim(D, "decode_attn_step", [&](auto d) {
+            LMX_LAUNCH((decode_attn_step_kernel<LMX_T(t), decltype(d)::value>), dim3((unsigned)(a.nh * a.n_split)), dim3(256), smem, st, a);
+        });
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -330,31 +331,33 @@ int decode_kv_attn_resident_slots(int dtype, int D, int K) {
     hipDeviceProp_t prop;
     LMX_CHECK_HIP(hipGetDevice(&dev));
     LMX_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-#define OC(TT, DD, NX) LMX_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_kv_attn_kernel<TT, DD, NX>, 256, smem))
-#define OCD(TT, DD) do { if (K <= 4096) OC(TT, DD, 2); else OC(TT, DD, 4); } while (0)
-    if (dtype == kBF16) { if (D == 128) OCD(bf16_t, 128); else OCD(bf16_t, 64); }
-    else { if (D == 128) OCD(f16_t, 128); else OCD(f16_t, 64); }
-#undef OCD
-#undef OC
+    dispatch_dtype16(dtype, "decode_kv_attn_resident_slots", [&](auto t) {
+        dispatch_head_dim(D, "decode_kv_attn_resident_slots", [&](auto d) {
+            constexpr int DD = decltype(d)::value;
+            const auto kern = K <= 4096 ? decode_kv_attn_kernel<LMX_T(t), DD, 2> : decode_kv_attn_kernel<LMX_T(t), DD, 4>;
+            LMX_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, smem));
+        });
+    });
     return per_cu * prop.multiProcessorCount;
 }
 
 void launch_decode_kv_attn(int dtype, int D, const DecAttnArgs& a, const GemvArgs& g, hipStream_t st) {
-    check_dec_attn(dtype, D, a, "decode_kv_attn");
-    LMX_REQUIRE(decode_kv_attn_applies(dtype, D, g), "decode_kv_attn: the k|v projection must be a plain 16-bit linear the hand-counted stream takes, K <= 8192");
-    LMX_REQUIRE(g.N == 2 * a.nkv * D && a.kv_gran && a.tag != 0, "decode_kv_attn: the projection's rows are k | v of every kv head; granules and a non-zero tag");
-    const size_t smem_g = gemv2_smem_bytes(g.K, 2), smem_a = dec_attn_smem_bytes(D);
-    const size_t smem = smem_g > smem_a ? smem_g : smem_a;
-    const int n_attn = a.nh * a.n_split;
-    // projection part: 2 rows per wave, 4 rounds in flight — the q|k|v shape's setting; (4, 4) / (4, 2) / (2, 8) / (1, 8) measured 21.1 -> 22.5 / 23.8 / 21.5 / 22.9 us
-    // per launch (profiles/r05_kv_attn_rp.txt): the launch is bound by its 86 MB at the streaming rate, not by workgroup count or bytes in flight
-    const dim3 grid((unsigned)(n_attn + cdiv(g.N, 8)));
-#define LK(TT, DD, NX) LMX_LAUNCH((decode_kv_attn_kernel<TT, DD, NX>), grid, dim3(256), smem, st, a, g, n_attn)
-#define LKD(TT, DD) do { if (g.K <= 4096) LK(TT, DD, 2); else LK(TT, DD, 4); } while (0)
-    if (dtype == kBF16) { if (D == 128) LKD(bf16_t, 128); else LKD(bf16_t, 64); }
-    else { if (D == 128) LKD(f16_t, 128); else LKD(f16_t, 64); }
-#undef LKD
-#undef LK
+    dispatch_dtype16(dtype, "decode_kv_attn", [&](auto t) {
+        check_dec_attn(D, a, "decode_kv_attn");
+        LMX_REQUIRE(decode_kv_attn_applies(dtype, D, g), "decode_kv_attn: the k|v projection must be a plain 16-bit linear the hand-counted stream takes, K <= 8192");
+        LMX_REQUIRE(g.N == 2 * a.nkv * D && a.kv_gran && a.tag != 0, "decode_kv_attn: the projection's rows are k | v of every kv head; granules and a non-zero tag");
+        const size_t smem_g = gemv2_smem_bytes(g.K, 2), smem_a = dec_attn_smem_bytes(D);
+        const size_t smem = smem_g > smem_a ? smem_g : smem_a;
+        const int n_attn = a.nh * a.n_split;
+        // projection part: 2 rows per wave, 4 rounds in flight — the q|k|v shape's setting; (4, 4) / (4, 2) / (2, 8) / (1, 8) measured 21.1 -> 22.5 / 23.8 / 21.5 / 22.9 us
+        // per launch (profiles/r05_kv_attn_rp.txt): the launch is bound by its 86 MB at the streaming rate, not by workgroup count or bytes in flight
+        const dim3 grid((unsigned)(n_attn + cdiv(g.N, 8)));
+        dispatch_head_dim(D, "decode_kv_attn", [&](auto d) {
+            constexpr int DD = decltype(d)::value;
+            const auto kern = g.K <= 4096 ? decode_kv_attn_kernel<LMX_T(t), DD, 2> : decode_kv_attn_kernel<LMX_T(t), DD, 4>;
+            LMX_LAUNCH(kern, grid, dim3(256), smem, st, a, g, n_attn);
+        });
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 

@@ -7,6 +7,7 @@
 //   im2col / clip_embed_ln  CLIPVisionEmbeddings + pre_layrnorm   HF5:models/clip/modeling_clip.py:138-218,642
 //   argmax_kernel         greedy sampling (temperature <= 0.001, llava/serve/model_worker.py:161)
 #include "common.h"
+#include "dispatch.h"
 #include "kernels.h"
 #include "engine.h"
 
@@ -79,17 +80,17 @@ void launch_rmsnorm(int dtype, const void* x, const void* w, void* y, int rows, 
     if (rows <= 0) return;
     if (H <= 8192) {
         const int np = (H / 8 + 255) / 256;            // 16-byte pieces per thread: 1 .. 4
-#define R(TT, NPV) hipLaunchKernelGGL((rmsnorm_reg_kernel<TT, NPV>), dim3(rows), dim3(256), 0, st, (const TT*)x, (const TT*)w, (TT*)y, H, ldx, ldy, eps)
-#define RT(TT) do { if (np == 1) R(TT, 1); else if (np == 2) R(TT, 2); else if (np == 3) R(TT, 3); else R(TT, 4); } while (0)
-        if (dtype == kBF16) RT(bf16_t); else if (dtype == kF16) RT(f16_t); else RT(float);
-#undef RT
-#undef R
+        dispatch_dtype(dtype, "rmsnorm", [&](auto t) {
+            using T = LMX_T(t);
+            const auto k = np == 1 ? rmsnorm_reg_kernel<T, 1> : np == 2 ? rmsnorm_reg_kernel<T, 2> : np == 3 ? rmsnorm_reg_kernel<T, 3> : rmsnorm_reg_kernel<T, 4>;
+            hipLaunchKernelGGL(k, dim3(rows), dim3(256), 0, st, (const T*)x, (const T*)w, (T*)y, H, ldx, ldy, eps);
+        });
         LMX_CHECK_HIP(hipGetLastError());
         return;
     }
-#define L(TT) hipLaunchKernelGGL(rmsnorm_kernel<TT>, dim3(rows), dim3(256), 0, st, (const TT*)x, (const TT*)w, (TT*)y, H, ldx, ldy, eps)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "rmsnorm", [&](auto t) {
+        hipLaunchKernelGGL(rmsnorm_kernel<LMX_T(t)>, dim3(rows), dim3(256), 0, st, (const LMX_T(t)*)x, (const LMX_T(t)*)w, (LMX_T(t)*)y, H, ldx, ldy, eps);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -174,17 +175,18 @@ void launch_layernorm(int dtype, const void* x, const void* w, const void* b, vo
     LMX_REQUIRE(H % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "layernorm: hidden size / strides must be multiples of 8");
     if (rows <= 0) return;
     if (dtype != kF32 && H % 512 == 0 && H <= 2048 && H != 1536) {
-#define LW(TT, NC) hipLaunchKernelGGL((layernorm_wave_kernel<TT, NC>), dim3(cdiv(rows, 4)), dim3(256), 0, st, (const TT*)x, (const TT*)w, (const TT*)b, (TT*)y, rows, ldx, ldy, eps)
-#define LWN(TT) do { if (H == 512) LW(TT, 1); else if (H == 1024) LW(TT, 2); else LW(TT, 4); } while (0)
-        if (dtype == kBF16) LWN(bf16_t); else LWN(f16_t);
-#undef LWN
-#undef LW
+        dispatch_dtype16(dtype, "layernorm", [&](auto t) {
+            using T = LMX_T(t);
+            const auto k = H == 512 ? layernorm_wave_kernel<T, 1> : H == 1024 ? layernorm_wave_kernel<T, 2> : layernorm_wave_kernel<T, 4>;
+            hipLaunchKernelGGL(k, dim3(cdiv(rows, 4)), dim3(256), 0, st, (const T*)x, (const T*)w, (const T*)b, (T*)y, rows, ldx, ldy, eps);
+        });
         LMX_CHECK_HIP(hipGetLastError());
         return;
     }
-#define L(TT) hipLaunchKernelGGL(layernorm_kernel<TT>, dim3(rows), dim3(256), 0, st, (const TT*)x, (const TT*)w, (const TT*)b, (TT*)y, H, ldx, ldy, eps)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "layernorm", [&](auto t) {
+        using T = LMX_T(t);
+        hipLaunchKernelGGL(layernorm_kernel<T>, dim3(rows), dim3(256), 0, st, (const T*)x, (const T*)w, (const T*)b, (T*)y, H, ldx, ldy, eps);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -269,11 +271,9 @@ void launch_rope_kv(int dtype, int D, const RopeKvArgs& a, hipStream_t st) {
     if (a.T <= 0) return;
     const dim3 grid(cdiv(a.T, 64), a.n_heads + 2 * a.n_kv_heads);
     const size_t smem = (size_t)64 * (D + 2) * dtype_size(dtype);
-#define L(TT, DD) hipLaunchKernelGGL((rope_kv_kernel<TT, DD>), grid, dim3(256), smem, st, a)
-    if (dtype == kBF16) { if (D == 128) L(bf16_t, 128); else L(bf16_t, 64); }
-    else if (dtype == kF16) { if (D == 128) L(f16_t, 128); else L(f16_t, 64); }
-    else { if (D == 128) L(float, 128); else L(float, 64); }
-#undef L
+    dispatch_dtype(dtype, "rope_kv", [&](auto t) {
+        dispatch_head_dim(D, "rope_kv", [&](auto d) { hipLaunchKernelGGL((rope_kv_kernel<LMX_T(t), decltype(d)::value>), grid, dim3(256), smem, st, a); });
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -299,9 +299,9 @@ __global__ __launch_bounds__(256) void gather_embed_kernel(const int* __restrict
 void launch_gather_embed(int dtype, const int* src, const void* table, const void* feats, void* out, int rows, int H, hipStream_t st) {
     LMX_REQUIRE(H % 8 == 0, "gather_embed: hidden size must be a multiple of 8");
     if (rows <= 0) return;
-#define L(TT) hipLaunchKernelGGL(gather_embed_kernel<TT>, dim3(rows), dim3(256), 0, st, src, (const TT*)table, (const TT*)feats, (TT*)out, H)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "gather_embed", [&](auto t) {
+        hipLaunchKernelGGL(gather_embed_kernel<LMX_T(t)>, dim3(rows), dim3(256), 0, st, src, (const LMX_T(t)*)table, (const LMX_T(t)*)feats, (LMX_T(t)*)out, H);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -321,9 +321,9 @@ __global__ __launch_bounds__(256) void gather_token_kernel(const int64_t* __rest
 void launch_gather_token(int dtype, const int64_t* tok_ptr, const void* table, void* out, int H, int vocab, hipStream_t st) {
     // the kernel copies the row in 16-byte pieces and clamps the id into [0, vocab): a width off that grid would lose its tail, an empty vocabulary would read row -1
     LMX_REQUIRE(H > 0 && H % 8 == 0 && vocab > 0, "gather_token: hidden size must be a positive multiple of 8 and the vocabulary non-empty");
-#define L(TT) hipLaunchKernelGGL(gather_token_kernel<TT>, dim3(2), dim3(256), 0, st, tok_ptr, (const TT*)table, (TT*)out, H, vocab)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "gather_token", [&](auto t) {
+        hipLaunchKernelGGL(gather_token_kernel<LMX_T(t)>, dim3(2), dim3(256), 0, st, tok_ptr, (const LMX_T(t)*)table, (LMX_T(t)*)out, H, vocab);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -354,9 +354,9 @@ void launch_im2col(int dtype, const void* pix, void* out, int N, int S, int ps, 
     LMX_REQUIRE(S % ps == 0 && kpad >= 3 * ps * ps, "im2col: bad geometry");
     const int P = (S / ps) * (S / ps);
     if (N <= 0) return;
-#define L(TT) hipLaunchKernelGGL(im2col_kernel<TT>, dim3(N * P), dim3(256), 0, st, (const TT*)pix, (TT*)out, S, ps, kpad)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "im2col", [&](auto t) {
+        hipLaunchKernelGGL(im2col_kernel<LMX_T(t)>, dim3(N * P), dim3(256), 0, st, (const LMX_T(t)*)pix, (LMX_T(t)*)out, S, ps, kpad);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -389,9 +389,10 @@ void launch_clip_embed_ln(int dtype, const void* patch, const void* cls, const v
                           void* y, int N, int P, int Dm, float eps, hipStream_t st) {
     if (N <= 0) return;
     const size_t smem = (size_t)Dm * 4;
-#define L(TT) hipLaunchKernelGGL(clip_embed_ln_kernel<TT>, dim3(N * (P + 1)), dim3(256), smem, st, (const TT*)patch, (const TT*)cls, (const TT*)pos, (const TT*)w, (const TT*)b, (TT*)y, P, Dm, eps)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "clip_embed_ln", [&](auto t) {
+        using T = LMX_T(t);
+        hipLaunchKernelGGL(clip_embed_ln_kernel<T>, dim3(N * (P + 1)), dim3(256), smem, st, (const T*)patch, (const T*)cls, (const T*)pos, (const T*)w, (const T*)b, (T*)y, P, Dm, eps);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -407,9 +408,9 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const T* __restrict__ sr
 void launch_copy_rows(int dtype, const void* src, void* dst, int N, int Ttot, int tok0, int P, int Dm, hipStream_t st) {
     LMX_REQUIRE(Dm % 8 == 0, "copy_rows: width must be a multiple of 8");
     if (N * P <= 0) return;
-#define L(TT) hipLaunchKernelGGL(copy_rows_kernel<TT>, dim3(N * P), dim3(256), 0, st, (const TT*)src, (TT*)dst, Ttot, tok0, P, Dm)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "copy_rows", [&](auto t) {
+        hipLaunchKernelGGL(copy_rows_kernel<LMX_T(t)>, dim3(N * P), dim3(256), 0, st, (const LMX_T(t)*)src, (LMX_T(t)*)dst, Ttot, tok0, P, Dm);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -448,23 +449,9 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const T* __restrict__ logi
 }
 
 void launch_argmax(int dtype, const void* logits, int V, int64_t* out_tok, hipStream_t st) {
-#define L(TT) hipLaunchKernelGGL(argmax_kernel<TT>, dim3(1), dim3(1024), 0, st, (const TT*)logits, V, out_tok)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
-    LMX_CHECK_HIP(hipGetLastError());
-}
-
-__global__ void advance_kernel(int* len_ptr, const int64_t* tok_ptr, int64_t* out_tokens, int* n_out_ptr, int max_out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        *len_ptr += 1;
-        const int n = *n_out_ptr;
-        if (out_tokens && n < max_out) out_tokens[n] = *tok_ptr;
-        *n_out_ptr = n + 1;
-    }
-}
-
-void launch_advance(int* len_ptr, const int64_t* tok_ptr, int64_t* out_tokens, int* n_out_ptr, int max_out, hipStream_t st) {
-    hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, st, len_ptr, tok_ptr, out_tokens, n_out_ptr, max_out);
+    dispatch_dtype(dtype, "argmax", [&](auto t) {
+        hipLaunchKernelGGL(argmax_kernel<LMX_T(t)>, dim3(1), dim3(1024), 0, st, (const LMX_T(t)*)logits, V, out_tok);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -485,9 +472,9 @@ __global__ __launch_bounds__(256) void gather_tokens_batch_kernel(const SeqState
 }
 
 void launch_gather_tokens_batch(int dtype, const SeqStateRef* tab, int n, const void* table, void* out, int H, int vocab, hipStream_t st) {
-#define L(TT) hipLaunchKernelGGL(gather_tokens_batch_kernel<TT>, dim3(2, n), dim3(256), 0, st, tab, (const TT*)table, (TT*)out, H, vocab)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "gather_tokens_batch", [&](auto t) {
+        hipLaunchKernelGGL(gather_tokens_batch_kernel<LMX_T(t)>, dim3(2, n), dim3(256), 0, st, tab, (const LMX_T(t)*)table, (LMX_T(t)*)out, H, vocab);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -509,9 +496,9 @@ __global__ __launch_bounds__(256) void interleave_half_kernel(const T* __restric
 
 void launch_interleave_half(int dtype, const void* src, void* dst, int I, int K, int half, hipStream_t st) {
     LMX_REQUIRE(I % 32 == 0 && K % 8 == 0, "interleave: intermediate size must be a multiple of 32");
-#define L(TT) hipLaunchKernelGGL(interleave_half_kernel<TT>, dim3(I), dim3(256), 0, st, (const TT*)src, (TT*)dst, K, half)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "interleave_half", [&](auto t) {
+        hipLaunchKernelGGL(interleave_half_kernel<LMX_T(t)>, dim3(I), dim3(256), 0, st, (const LMX_T(t)*)src, (LMX_T(t)*)dst, K, half);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -601,18 +588,13 @@ __global__ __launch_bounds__(256) void cast_kernel(const S* __restrict__ s, Dt* 
 void launch_cast(int sd, int dd, const void* src, void* dst, size_t n, hipStream_t st) {
     if (n == 0) return;
     const int grid = (int)(cdiv64((int64_t)n, 256) < 4096 ? cdiv64((int64_t)n, 256) : 4096);
-#define L(SS, DD) hipLaunchKernelGGL((cast_kernel<SS, DD>), dim3(grid), dim3(256), 0, st, (const SS*)src, (DD*)dst, n)
-    if (sd == kF32 && dd == kBF16) L(float, bf16_t);
-    else if (sd == kF32 && dd == kF16) L(float, f16_t);
-    else if (sd == kBF16 && dd == kF32) L(bf16_t, float);
-    else if (sd == kF16 && dd == kF32) L(f16_t, float);
-    else if (sd == kF32 && dd == kF32) L(float, float);
-    else if (sd == kBF16 && dd == kBF16) L(bf16_t, bf16_t);
-    else if (sd == kF16 && dd == kF16) L(f16_t, f16_t);
-    else if (sd == kBF16 && dd == kF16) L(bf16_t, f16_t);
-    else if (sd == kF16 && dd == kBF16) L(f16_t, bf16_t);
-    else throw Error{"cast: unsupported dtype pair"};
-#undef L
+    dispatch_dtype(sd, "cast (source)", [&](auto s) {
+        using S = typename decltype(s)::type;
+        dispatch_dtype(dd, "cast (destination)", [&](auto d) {
+            using Dt = typename decltype(d)::type;
+            hipLaunchKernelGGL((cast_kernel<S, Dt>), dim3(grid), dim3(256), 0, st, (const S*)src, (Dt*)dst, n);
+        });
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 

@@ -19,6 +19,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
 #include "kernels.h"
 #include <cstring>
 #include "gemm_common.h"
@@ -748,9 +749,7 @@ void launch_gemm(int dtype, const GemmArgs& a, int variant, hipStream_t st) {
     }
     LMX_REQUIRE(a.K % GEMM_BK == 0, "gemm: K must be a multiple of 64 (pad the operand)");
     LMX_REQUIRE(a.ldx % 8 == 0 && a.ldw % 8 == 0 && a.ldc % 4 == 0, "gemm: leading dims must keep 16-byte row alignment");
-    if (dtype == kBF16) launch_gemm16<bf16_t>(a, variant, st);
-    else if (dtype == kF16) launch_gemm16<f16_t>(a, variant, st);
-    else throw Error{"gemm: bad dtype"};
+    dispatch_dtype16(dtype, "gemm", [&](auto t) { launch_gemm16<LMX_T(t)>(a, variant, st); });      // (fp32 left above)
 }
 
 template <typename T, int MB, int R>
@@ -840,10 +839,7 @@ void launch_gemv(int dtype, const GemvArgs& a, int MB, hipStream_t st) {
     LMX_REQUIRE(a.ldw >= a.K && ((size_t)a.ldw * es) % 16 == 0 && reinterpret_cast<uintptr_t>(a.W) % 16 == 0, "gemv: weight rows must be 16-byte aligned");
     LMX_REQUIRE(MB == 1 || (a.ldx >= a.K && ((size_t)a.ldx * es) % 16 == 0), "gemv: x rows must be 16-byte aligned");
     LMX_REQUIRE(reinterpret_cast<uintptr_t>(a.X) % 16 == 0 && reinterpret_cast<uintptr_t>(a.norm_w) % 16 == 0, "gemv: x and the norm weights must be 16-byte aligned");
-    if (dtype == kBF16) launch_gemv_t<bf16_t>(a, MB, st);
-    else if (dtype == kF16) launch_gemv_t<f16_t>(a, MB, st);
-    else if (dtype == kF32) launch_gemv_t<float>(a, MB, st);
-    else throw Error{"gemv: bad dtype"};
+    dispatch_dtype(dtype, "gemv", [&](auto t) { launch_gemv_t<LMX_T(t)>(a, MB, st); });
 }
 
 }  // namespace lmx

@@ -36,6 +36,7 @@
 #include <set>
 
 #include "common.h"
+#include "dispatch.h"
 #include "kernels.h"
 #include "gemm_common.h"
 
@@ -629,9 +630,7 @@ static void launch_gemm8p_t(GemmArgs a, hipStream_t st) {
 }
 
 void launch_gemm8p(int dtype, const GemmArgs& a, hipStream_t st) {
-    if (dtype == kBF16) launch_gemm8p_t<bf16_t>(a, st);
-    else if (dtype == kF16) launch_gemm8p_t<f16_t>(a, st);
-    else throw Error{"gemm8p: 16-bit dtypes only"};
+    dispatch_dtype16(dtype, "gemm8p", [&](auto t) { launch_gemm8p_t<LMX_T(t)>(a, st); });
 }
 
 }  // namespace lmx

@@ -25,6 +25,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "dispatch.h"
 #include "kernels.h"
 #include "gemm_common.h"
 
@@ -231,22 +232,21 @@ bool gemm_wgrad_direct_ok(int dtype, int M, int N, int rows, int ldx, int ldw, i
 }
 
 void launch_gemm_wgrad(int dtype, const void* dy, int lddy, const void* x, int ldx, int rows, int M, int N, void* out, int ldo, hipStream_t st) {
-    LMX_REQUIRE(gemm_wgrad_direct_ok(dtype, M, N, rows, lddy, ldx, ldo),
-                "gemm_wgrad: 16-bit operands, out features and in features multiples of 256, rows a multiple of 64, 16-byte aligned row strides, operands below 4 GiB");
-    LMX_REQUIRE(((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 7) == 0, "gemm_wgrad: operands must be 16-byte aligned");
-    GemmArgs a{};
-    a.X = dy; a.W = x; a.C = out; a.M = M; a.N = N; a.K = rows; a.ldx = lddy; a.ldw = ldx; a.ldc = ldo;
-    const int tiles = (M >> 8) * (N >> 8);
-    static std::once_flag once;                       // both instantiations decay to the same pointer type: opt both in at once
-    std::call_once(once, [] {
-        LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8t_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS));
-        LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8t_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS));
-    });
-    auto launch = [&](auto kern) {
-        LMX_LAUNCH(kern, dim3(tiles), dim3(512), T8_LDS, st, a);
+    dispatch_dtype16(dtype, "gemm_wgrad", [&](auto t) {      // first: the shape rule below would report a bad dtype code as a bad shape
+        LMX_REQUIRE(gemm_wgrad_direct_ok(dtype, M, N, rows, lddy, ldx, ldo),
+                    "gemm_wgrad: 16-bit operands, out features and in features multiples of 256, rows a multiple of 64, 16-byte aligned row strides, operands below 4 GiB");
+        LMX_REQUIRE(((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 7) == 0, "gemm_wgrad: operands must be 16-byte aligned");
+        GemmArgs a{};
+        a.X = dy; a.W = x; a.C = out; a.M = M; a.N = N; a.K = rows; a.ldx = lddy; a.ldw = ldx; a.ldc = ldo;
+        const int tiles = (M >> 8) * (N >> 8);
+        static std::once_flag once;                       // both instantiations decay to the same pointer type: opt both in at once
+        std::call_once(once, [] {
+            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8t_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS));
+            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8t_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS));
+        });
+        LMX_LAUNCH(gemm8t_kernel<LMX_T(t)>, dim3(tiles), dim3(512), T8_LDS, st, a);
         LMX_CHECK_HIP(hipGetLastError());
-    };
-    if (dtype == kBF16) launch(gemm8t_kernel<bf16_t>); else launch(gemm8t_kernel<f16_t>);
+    });
 }
 
 }  // namespace lmx

@@ -223,8 +223,6 @@ void launch_copy_rows(int dtype, const void* src, void* dst, int N, int Ttot, in
 
 // greedy sampling: token = argmax(logits[0..V)), first index wins ties (torch.argmax semantics)
 void launch_argmax(int dtype, const void* logits, int V, int64_t* out_tok, hipStream_t st);
-// decode-loop bookkeeping: *len += 1 ; tokens_out[*n_out++] = *tok
-void launch_advance(int* len_ptr, const int64_t* tok_ptr, int64_t* out_tokens, int* n_out_ptr, int max_out, hipStream_t st);
 
 // ---- decode batch (continuous batching): per-sequence device state, one table row per member -------------------------
 // how a sequence picks its next token on the device: temperature <= 0 -> greedy argmax, else temperature / top-k / top-p draw

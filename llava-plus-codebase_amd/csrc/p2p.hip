@@ -14,6 +14,7 @@
 //   One workgroup per row: push the row to all peers (16-byte stores) -> __threadfence_system -> flag stores (system scope)
 //   -> spin on the local flags (bounded: 30 s of the 100 MHz realtime counter, then status := k) -> sum slots in rank order.
 #include "common.h"
+#include "dispatch.h"
 #include "kernels.h"
 
 namespace lmx {
@@ -125,9 +126,7 @@ void launch_p2p_allreduce(int dtype, const P2PLaunch& l, hipStream_t st) {
     a.flags_off = p2p_flags_offset(l.world, l.H, (int)es);
     a.status_off = a.flags_off + (size_t)2 * l.world * P2P_MAX_ROWS * 4;
     for (int p = 0; p < l.world; ++p) a.peer[p] = static_cast<char*>(l.peer[p]);
-#define L(TT) hipLaunchKernelGGL(p2p_allreduce_kernel<TT>, dim3(l.rows), dim3(256), 0, st, a)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "p2p_allreduce", [&](auto t) { hipLaunchKernelGGL(p2p_allreduce_kernel<LMX_T(t)>, dim3(l.rows), dim3(256), 0, st, a); });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -282,9 +281,7 @@ void launch_p2p_allreduce_big(int dtype, const P2PBigLaunch& l, hipStream_t st) 
     constexpr int max_wgs = 64;      // 64 fat workgroups: 349 -> 88 us per 8.9 MB sum (profiles/r04_p2p_big_wgs.txt)
     const int n_slices = (int)(chunk / P2P_BIG_SLICE);
     const int grid = n_slices < max_wgs ? n_slices : max_wgs;
-#define L(TT) hipLaunchKernelGGL(p2p_allreduce_big_kernel<TT>, dim3(grid), dim3(256), 0, st, a)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "p2p_allreduce_big", [&](auto t) { hipLaunchKernelGGL(p2p_allreduce_big_kernel<LMX_T(t)>, dim3(grid), dim3(256), 0, st, a); });
     LMX_CHECK_HIP(hipGetLastError());
 }
 

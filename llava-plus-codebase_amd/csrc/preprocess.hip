@@ -12,6 +12,7 @@
 #include <cmath>
 #include <vector>
 #include "common.h"
+#include "dispatch.h"
 #include "kernels.h"
 
 namespace lmx {
@@ -174,9 +175,7 @@ size_t launch_preprocess(int dtype, const uint8_t* rgb, int H, int W, int size, 
     a.bounds_h = d; a.kk_h = d + bh.size(); a.bounds_v = a.kk_h + kh.size(); a.kk_v = a.bounds_v + bv.size();
     a.tmp = static_cast<uint8_t*>(scratch) + tab_bytes;
     hipLaunchKernelGGL(pre_resize_h_kernel, dim3(cdiv(a.CH * size, 256)), dim3(256), 0, st, a);
-#define L(TT) hipLaunchKernelGGL(pre_resize_v_norm_kernel<TT>, dim3(cdiv(size * size, 256)), dim3(256), 0, st, a, (TT*)out)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "preprocess", [&](auto t) { hipLaunchKernelGGL(pre_resize_v_norm_kernel<LMX_T(t)>, dim3(cdiv(size * size, 256)), dim3(256), 0, st, a, (LMX_T(t)*)out); });
     LMX_CHECK_HIP(hipGetLastError());
     LMX_CHECK_HIP(hipStreamSynchronize(st));     // the host coefficient tables must outlive their upload
     return need;

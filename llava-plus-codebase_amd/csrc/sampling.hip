@@ -17,6 +17,7 @@
 // torch.multinomial draws differently (exponential race), so ids are not comparable with a torch run for the same seed;
 // tests check the survivor set against HF's own warpers and the drawn id against the float64 inverse CDF for the same u.
 #include "common.h"
+#include "dispatch.h"
 #include "kernels.h"
 
 namespace lmx {
@@ -320,12 +321,11 @@ __global__ __launch_bounds__(CPT > 0 ? FAST_NT : 1024) void sample_kernel(const 
 void launch_sample(int dtype, const void* logits, int V, const SampleParams& p, const int* offset_ptr, int64_t* out_tok,
                    const uint32_t* u32_override, uint8_t* keep_out, hipStream_t st) {
     LMX_REQUIRE(V > 0 && p.temperature > 0.f && p.top_p > 0.f, "sample: temperature and top_p must be positive");
-#define L2(TT, CC) hipLaunchKernelGGL((sample_kernel<TT, CC>), dim3(1), dim3(CC > 0 ? FAST_NT : 1024), 0, st, (const TT*)logits, V, p, offset_ptr, \
-                                     u32_override ? *u32_override : 0u, u32_override ? 1 : 0, out_tok, keep_out)
-#define L(TT) do { if (sample_cpt(V) == 32) L2(TT, 32); else L2(TT, 0); } while (0)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
-#undef L2
+    dispatch_dtype(dtype, "sample", [&](auto t) {
+        const auto kern = sample_cpt(V) == 32 ? sample_kernel<LMX_T(t), 32> : sample_kernel<LMX_T(t), 0>;
+        hipLaunchKernelGGL(kern, dim3(1), dim3(sample_cpt(V) > 0 ? FAST_NT : 1024), 0, st, (const LMX_T(t)*)logits, V, p, offset_ptr,
+                           u32_override ? *u32_override : 0u, u32_override ? 1 : 0, out_tok, keep_out);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -399,12 +399,12 @@ void launch_argmax_advance_batch(int dtype, const void* logits, int V, int ld, c
                                  const void* embed, void* h_out, int H, hipStream_t st) {
     LMX_REQUIRE((tab != nullptr) != (single != nullptr) && (tab || n == 1), "pick: give a device table or one by-value state");
     const SeqStateRef one = single ? *single : SeqStateRef{};
-#define L2(TT, CC) hipLaunchKernelGGL((pick_advance_batch_kernel<TT, CC>), dim3(n), dim3(CC > 0 ? FAST_NT : 1024), 0, st, (const TT*)logits, V, ld, tab, one, \
-                                      ids_out, (const TT*)embed, (TT*)h_out, H)
-#define L(TT) do { if (sample_cpt(V) == 32) L2(TT, 32); else L2(TT, 0); } while (0)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
-#undef L2
+    dispatch_dtype(dtype, "argmax_advance_batch", [&](auto t) {
+        using T = LMX_T(t);
+        const auto kern = sample_cpt(V) == 32 ? pick_advance_batch_kernel<T, 32> : pick_advance_batch_kernel<T, 0>;
+        hipLaunchKernelGGL(kern, dim3(n), dim3(sample_cpt(V) > 0 ? FAST_NT : 1024), 0, st, (const T*)logits, V, ld, tab, one,
+                           ids_out, (const T*)embed, (T*)h_out, H);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -540,18 +540,18 @@ void launch_beam_gumbel_topk(int dtype, const void* logits, int ld, int V, int r
                              uint32_t counter0, int K, float* out_keys, float* out_scores, int* out_ids, hipStream_t st) {
     LMX_REQUIRE(rows >= 1 && K >= 1 && K <= 64 && V >= 1 && temperature > 0.f, "beam_gumbel_topk: bad arguments");
     const float inv_t = 1.f / fmaxf(temperature, 1e-5f);
-#define L(TT) hipLaunchKernelGGL(beam_gumbel_topk_kernel<TT>, dim3(rows), dim3(1024), 0, st, (const TT*)logits, ld, V, keep, beam_scores, inv_t, (uint32_t)seed, \
-                                 (uint32_t)(seed >> 32), counter0, K, out_keys, out_scores, out_ids)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "beam_gumbel_topk", [&](auto t) {
+        hipLaunchKernelGGL(beam_gumbel_topk_kernel<LMX_T(t)>, dim3(rows), dim3(1024), 0, st, (const LMX_T(t)*)logits, ld, V, keep, beam_scores, inv_t, (uint32_t)seed,
+                           (uint32_t)(seed >> 32), counter0, K, out_keys, out_scores, out_ids);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
 void launch_beam_topk(int dtype, const void* logits, int ld, int V, int rows, const float* beam_scores, int K, float* out_scores, int* out_ids, hipStream_t st) {
     LMX_REQUIRE(rows >= 1 && K >= 1 && K <= 64 && V >= 1, "beam_topk: bad arguments");
-#define L(TT) hipLaunchKernelGGL(beam_topk_kernel<TT>, dim3(rows), dim3(1024), 0, st, (const TT*)logits, ld, V, beam_scores, K, out_scores, out_ids)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "beam_topk", [&](auto t) {
+        hipLaunchKernelGGL(beam_topk_kernel<LMX_T(t)>, dim3(rows), dim3(1024), 0, st, (const LMX_T(t)*)logits, ld, V, beam_scores, K, out_scores, out_ids);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 

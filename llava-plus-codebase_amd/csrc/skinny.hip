@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "dispatch.h"
 #include "kernels.h"
 #include "wstream.h"
 
@@ -362,21 +363,20 @@ size_t skinny_swizzled_bytes(int N, int K, int es) {
 }
 
 void launch_skinny_swizzle(int dtype, const void* W, int ldw, void* dst, int N, int K, hipStream_t st) {
-    LMX_REQUIRE(dtype == kBF16 || dtype == kF16, "skinny swizzle: 16-bit weights only");
     LMX_REQUIRE(K % 8 == 0 && ldw % 8 == 0, "skinny swizzle: K must be a multiple of 8");
     const dim3 grid(cdiv(K, SK_SUPER), cdiv(N, 16));
-    if (dtype == kBF16) hipLaunchKernelGGL(skinny_swizzle_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)W, ldw, (char*)dst, N, K, cdiv(K, SK_SUPER));
-    else hipLaunchKernelGGL(skinny_swizzle_kernel<f16_t>, grid, dim3(256), 0, st, (const f16_t*)W, ldw, (char*)dst, N, K, cdiv(K, SK_SUPER));
+    dispatch_dtype16(dtype, "skinny_swizzle", [&](auto t) {
+        hipLaunchKernelGGL(skinny_swizzle_kernel<LMX_T(t)>, grid, dim3(256), 0, st, (const LMX_T(t)*)W, ldw, (char*)dst, N, K, cdiv(K, SK_SUPER));
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
 void launch_skinny_gemm(int dtype, const GemmArgs& a, hipStream_t st) {
-    LMX_REQUIRE(dtype == kBF16 || dtype == kF16, "skinny gemm: 16-bit operands only (the fp32 verification engine batches through the GEMV)");
     LMX_REQUIRE(a.M >= 1 && a.M <= 32, "skinny gemm: 1..32 token rows");
     LMX_REQUIRE(a.N > 0 && a.K > 0 && a.K % 32 == 0, "skinny gemm: K must be a multiple of 32");
     LMX_REQUIRE(a.ldx % 8 == 0 && a.ldw % 8 == 0, "skinny gemm: leading dims must keep 16-byte row alignment");
     if (a.act == kActSiluMul) LMX_REQUIRE(a.N % 64 == 0, "skinny gemm: SiLU·mul needs N (fused gate|up rows) % 64 == 0");
-    if (dtype == kBF16) launch_skinny_t<bf16_t>(a, st); else launch_skinny_t<f16_t>(a, st);
+    dispatch_dtype16(dtype, "skinny_gemm", [&](auto t) { launch_skinny_t<LMX_T(t)>(a, st); });      // (the fp32 verification engine batches through the GEMV)
 }
 
 }  // namespace lmx

@@ -20,6 +20,7 @@
 
 #include <mutex>
 #include "common.h"
+#include "dispatch.h"
 #include "kernels.h"
 #include "engine.h"
 
@@ -90,18 +91,18 @@ void launch_ce_loss_fwd(int dtype, const void* logits, int ld, const int64_t* la
                         float* row_loss, float* out2, hipStream_t st) {
     LMX_REQUIRE(B >= 1 && Tlen >= 2 && V >= 1, "ce_loss: need at least two positions per sequence");
     const int R = B * (Tlen - 1);
-#define L(TT) hipLaunchKernelGGL(ce_fwd_kernel<TT>, dim3(R), dim3(256), 0, st, (const TT*)logits, ld, labels, Tlen, V, ignore, lse, row_loss)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "ce_loss_fwd", [&](auto t) {
+        hipLaunchKernelGGL(ce_fwd_kernel<LMX_T(t)>, dim3(R), dim3(256), 0, st, (const LMX_T(t)*)logits, ld, labels, Tlen, V, ignore, lse, row_loss);
+    });
     hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, labels, B, Tlen, V, ignore, out2);
     LMX_CHECK_HIP(hipGetLastError());
 }
 
 void launch_ce_loss_bwd(int dtype, const void* logits, int ld, const int64_t* labels, int B, int Tlen, int V, int64_t ignore, const float* lse,
                         const float* out2, float grad, void* dlogits, int ldd, hipStream_t st) {
-#define L(TT) hipLaunchKernelGGL(ce_bwd_kernel<TT>, dim3(B * Tlen), dim3(256), 0, st, (const TT*)logits, ld, labels, Tlen, V, ignore, lse, out2, grad, (TT*)dlogits, ldd)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "ce_loss_bwd", [&](auto t) {
+        hipLaunchKernelGGL(ce_bwd_kernel<LMX_T(t)>, dim3(B * Tlen), dim3(256), 0, st, (const LMX_T(t)*)logits, ld, labels, Tlen, V, ignore, lse, out2, grad, (LMX_T(t)*)dlogits, ldd);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -268,27 +269,24 @@ void launch_rmsnorm_bwd(int dtype, const void* x, const void* w, const void* dy,
     float* part = dw ? inv_scratch + (((size_t)rows + 63) / 64) * 64 : nullptr;
     const bool aligned = (((uintptr_t)x | (uintptr_t)w | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)residual) & 15) == 0;
     if (dtype != kF32 && aligned && (H == 1024 || H == 2048 || H == 4096)) {
-#define F(TT, NC) hipLaunchKernelGGL((rmsnorm_bwd_fused_kernel<TT, NC>), dim3(nblk), dim3(512), 0, st, (const TT*)x, (const TT*)w, (const TT*)dy, (const TT*)residual, \
-                                     (TT*)dx, part, rows, eps)
-#define FT(TT) do { if (H == 1024) F(TT, 2); else if (H == 2048) F(TT, 4); else F(TT, 8); } while (0)
-        if (dtype == kBF16) FT(bf16_t); else FT(f16_t);
-#undef FT
-#undef F
+        dispatch_dtype16(dtype, "rmsnorm_bwd", [&](auto t) {
+            using T = LMX_T(t);
+            const auto kern = H == 1024 ? rmsnorm_bwd_fused_kernel<T, 2> : H == 2048 ? rmsnorm_bwd_fused_kernel<T, 4> : rmsnorm_bwd_fused_kernel<T, 8>;
+            hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), 0, st, (const T*)x, (const T*)w, (const T*)dy, (const T*)residual, (T*)dx, part, rows, eps);
+        });
         if (dw) hipLaunchKernelGGL(rmsnorm_bwd_dw_sum_kernel, dim3(cdiv(H, 256)), dim3(256), 0, st, part, nblk, H, dw);
         LMX_CHECK_HIP(hipGetLastError());
         return;
     }
-#define L(TT)                                                                                                                              \
-    do {                                                                                                                                   \
-        hipLaunchKernelGGL(rmsnorm_bwd_dx_kernel<TT>, dim3(rows), dim3(256), 0, st, (const TT*)x, (const TT*)w, (const TT*)dy, (TT*)dx, H, eps);   \
-        if (dw) {                                                                                                                          \
-            hipLaunchKernelGGL(rms_inv_kernel<TT>, dim3(rows), dim3(256), 0, st, (const TT*)x, inv_scratch, H, eps);                       \
-            hipLaunchKernelGGL(rmsnorm_bwd_dw_part_kernel<TT>, dim3(cdiv(H, 64), nblk), dim3(256), 0, st, (const TT*)x, (const TT*)dy, inv_scratch, part, rows, H, RPB); \
-            hipLaunchKernelGGL(rmsnorm_bwd_dw_sum_kernel, dim3(cdiv(H, 256)), dim3(256), 0, st, part, nblk, H, dw);                        \
-        }                                                                                                                                  \
-    } while (0)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "rmsnorm_bwd", [&](auto t) {
+        using T = LMX_T(t);
+        hipLaunchKernelGGL(rmsnorm_bwd_dx_kernel<T>, dim3(rows), dim3(256), 0, st, (const T*)x, (const T*)w, (const T*)dy, (T*)dx, H, eps);
+        if (dw) {
+            hipLaunchKernelGGL(rms_inv_kernel<T>, dim3(rows), dim3(256), 0, st, (const T*)x, inv_scratch, H, eps);
+            hipLaunchKernelGGL(rmsnorm_bwd_dw_part_kernel<T>, dim3(cdiv(H, 64), nblk), dim3(256), 0, st, (const T*)x, (const T*)dy, inv_scratch, part, rows, H, RPB);
+            hipLaunchKernelGGL(rmsnorm_bwd_dw_sum_kernel, dim3(cdiv(H, 256)), dim3(256), 0, st, part, nblk, H, dw);
+        }
+    });
     LMX_CHECK_HIP(hipGetLastError());
     if (residual) launch_elementwise(dtype, 3 /* add */, residual, dx, dx, (size_t)rows * H, st);      // the shapes the fused kernel does not take: dx = residual + dx
 }
@@ -327,18 +325,20 @@ void launch_swiglu_bwd(int dtype, const void* g, const void* u, const void* dact
     if (!n) return;
     if (dtype != kF32 && ((((uintptr_t)g | (uintptr_t)u | (uintptr_t)dact | (uintptr_t)dg | (uintptr_t)du) & 15) == 0)) {
         const size_t n8 = n / 8, tail = n - n8 * 8;
-#define V(TT) do { if (n8) hipLaunchKernelGGL(swiglu_bwd8_kernel<TT>, dim3((unsigned)cdiv64((int64_t)n8, 256)), dim3(256), 0, st, (const TT*)g, (const TT*)u, (const TT*)dact, \
-                                              (TT*)dg, (TT*)du, n8);                                                                                                   \
-                   if (tail) hipLaunchKernelGGL(swiglu_bwd_kernel<TT>, dim3(1), dim3(256), 0, st, (const TT*)g + n8 * 8, (const TT*)u + n8 * 8, (const TT*)dact + n8 * 8, \
-                                                (TT*)dg + n8 * 8, (TT*)du + n8 * 8, tail); } while (0)
-        if (dtype == kBF16) V(bf16_t); else V(f16_t);
-#undef V
+        dispatch_dtype16(dtype, "swiglu_bwd", [&](auto t) {
+            using T = LMX_T(t);
+            if (n8) hipLaunchKernelGGL(swiglu_bwd8_kernel<T>, dim3((unsigned)cdiv64((int64_t)n8, 256)), dim3(256), 0, st, (const T*)g, (const T*)u, (const T*)dact,
+                                       (T*)dg, (T*)du, n8);
+            if (tail) hipLaunchKernelGGL(swiglu_bwd_kernel<T>, dim3(1), dim3(256), 0, st, (const T*)g + n8 * 8, (const T*)u + n8 * 8, (const T*)dact + n8 * 8,
+                                         (T*)dg + n8 * 8, (T*)du + n8 * 8, tail);
+        });
         LMX_CHECK_HIP(hipGetLastError());
         return;
     }
-#define L(TT) hipLaunchKernelGGL(swiglu_bwd_kernel<TT>, dim3((unsigned)cdiv64((int64_t)n, 256)), dim3(256), 0, st, (const TT*)g, (const TT*)u, (const TT*)dact, (TT*)dg, (TT*)du, n)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "swiglu_bwd", [&](auto t) {
+        using T = LMX_T(t);
+        hipLaunchKernelGGL(swiglu_bwd_kernel<T>, dim3((unsigned)cdiv64((int64_t)n, 256)), dim3(256), 0, st, (const T*)g, (const T*)u, (const T*)dact, (T*)dg, (T*)du, n);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -365,9 +365,9 @@ __global__ __launch_bounds__(256) void rope_bwd_kernel(const T* __restrict__ dy,
 void launch_rope_bwd(int dtype, const void* dy, void* dx, const float* cos_sin, int pos0, int Tn, int heads, int D, int ld, hipStream_t st) {
     const size_t total = (size_t)Tn * heads * (D / 2);
     if (!total) return;
-#define L(TT) hipLaunchKernelGGL(rope_bwd_kernel<TT>, dim3((unsigned)cdiv64((int64_t)total, 256)), dim3(256), 0, st, (const TT*)dy, (TT*)dx, cos_sin, pos0, heads, D, ld, Tn)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "rope_bwd", [&](auto t) {
+        hipLaunchKernelGGL(rope_bwd_kernel<LMX_T(t)>, dim3((unsigned)cdiv64((int64_t)total, 256)), dim3(256), 0, st, (const LMX_T(t)*)dy, (LMX_T(t)*)dx, cos_sin, pos0, heads, D, ld, Tn);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -423,15 +423,16 @@ __global__ __launch_bounds__(256) void transpose16_vec_kernel(const uint16_t* __
 void launch_transpose(int dtype, const void* src, int ld, int rows, int cols, void* dst, int ldd, hipStream_t st) {
     if (rows <= 0 || cols <= 0) return;
     const bool vec = dtype != kF32 && rows % 8 == 0 && cols % 8 == 0 && ld % 8 == 0 && ldd % 8 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0;
-    if (vec) {
-        hipLaunchKernelGGL(transpose16_vec_kernel, dim3(cdiv(cols, 128), cdiv(rows, 64)), dim3(256), 0, st, (const uint16_t*)src, ld, rows, cols, (uint16_t*)dst, ldd);
+    if (vec) {      // untyped 16-bit kernel: the dispatch only refuses a code that is neither 16-bit type
+        dispatch_dtype16(dtype, "transpose", [&](auto) { hipLaunchKernelGGL(transpose16_vec_kernel, dim3(cdiv(cols, 128), cdiv(rows, 64)), dim3(256), 0, st,
+                                                                            (const uint16_t*)src, ld, rows, cols, (uint16_t*)dst, ldd); });
         LMX_CHECK_HIP(hipGetLastError());
         return;
     }
     const dim3 grid(cdiv(cols, 64), cdiv(rows, 64));
-#define L(TT) hipLaunchKernelGGL(transpose_kernel<TT>, grid, dim3(256), 0, st, (const TT*)src, ld, rows, cols, (TT*)dst, ldd)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "transpose", [&](auto t) {
+        hipLaunchKernelGGL(transpose_kernel<LMX_T(t)>, grid, dim3(256), 0, st, (const LMX_T(t)*)src, ld, rows, cols, (LMX_T(t)*)dst, ldd);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -622,19 +623,18 @@ void launch_attn_bwd(int dtype, int D, const void* q, const void* k, const void*
     const size_t smem = (size_t)2 * QB * Tn * sizeof(float);
     LMX_REQUIRE(smem <= 120 * 1024, "attn_bwd: sequence too long for the parity kernel (<= 15360 positions)");
     constexpr int KB = 4;
-#define L2(TT, DD)                                                                                                                                  \
-    do {                                                                                                                                           \
-        auto kern = QB == 4 ? attn_bwd_dq_kernel<TT, DD, 4> : attn_bwd_dq_kernel<TT, DD, 1>;                                                       \
-        LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));          \
-        hipLaunchKernelGGL(kern, dim3(cdiv(Tn, QB), heads), dim3(256), smem, st, (const TT*)q, (const TT*)k, (const TT*)v, (const TT*)dO, (TT*)dq, lse, delta, Tn, \
-                           heads, kv_heads, ldq, ldk, ldo, scale);                                                                                 \
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<TT, DD, KB>), dim3(cdiv(Tn, KB), kv_heads), dim3(256), 0, st, (const TT*)q, (const TT*)k, (const TT*)v,  \
-                           (const TT*)dO, lse, delta, (TT*)dk, (TT*)dv, Tn, heads, kv_heads, ldq, ldk, ldo, scale);                                \
-    } while (0)
-#define L(TT) do { if (D == 128) L2(TT, 128); else L2(TT, 64); } while (0)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
-#undef L2
+    dispatch_dtype(dtype, "attn_bwd", [&](auto t) {
+        using T = LMX_T(t);
+        dispatch_head_dim(D, "attn_bwd", [&](auto d) {
+            constexpr int DD = decltype(d)::value;
+            auto kern = QB == 4 ? attn_bwd_dq_kernel<T, DD, 4> : attn_bwd_dq_kernel<T, DD, 1>;
+            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
+            hipLaunchKernelGGL(kern, dim3(cdiv(Tn, QB), heads), dim3(256), smem, st, (const T*)q, (const T*)k, (const T*)v, (const T*)dO, (T*)dq, lse, delta, Tn,
+                               heads, kv_heads, ldq, ldk, ldo, scale);
+            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, DD, KB>), dim3(cdiv(Tn, KB), kv_heads), dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v,
+                               (const T*)dO, lse, delta, (T*)dk, (T*)dv, Tn, heads, kv_heads, ldq, ldk, ldo, scale);
+        });
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -700,30 +700,30 @@ void launch_elementwise(int dtype, int op, const void* a, const void* b, void* o
     const size_t n8 = vec ? n / 8 : 0, done = n8 * 8;
     if (n8) {
         const dim3 g8((unsigned)cdiv64((int64_t)n8, 256));
-#define V2(TT, OP) hipLaunchKernelGGL((ew8_kernel<TT, OP>), g8, dim3(256), 0, st, (const TT*)a, (const TT*)b, (TT*)out, n8)
-#define V(TT) do { if (op == 0) V2(TT, 0); else if (op == 1) V2(TT, 1); else if (op == 2) V2(TT, 2); else V2(TT, 3); } while (0)
-        if (dtype == kBF16) V(bf16_t); else V(f16_t);
-#undef V
-#undef V2
+        dispatch_dtype16(dtype, "elementwise", [&](auto t) {
+            using T = LMX_T(t);
+            const auto kern = op == 0 ? ew8_kernel<T, 0> : op == 1 ? ew8_kernel<T, 1> : op == 2 ? ew8_kernel<T, 2> : ew8_kernel<T, 3>;
+            hipLaunchKernelGGL(kern, g8, dim3(256), 0, st, (const T*)a, (const T*)b, (T*)out, n8);
+        });
     }
     if (done < n) {
         const size_t es = dtype == kF32 ? 4 : 2, rest = n - done;
         const char* a2 = static_cast<const char*>(a) + done * es; const char* b2 = b ? static_cast<const char*>(b) + done * es : nullptr; char* o2 = static_cast<char*>(out) + done * es;
         const dim3 grid((unsigned)cdiv64((int64_t)rest, 256));
-#define L2(TT, OP) hipLaunchKernelGGL((ew_kernel<TT, OP>), grid, dim3(256), 0, st, (const TT*)a2, (const TT*)b2, (TT*)o2, rest)
-#define L(TT) do { if (op == 0) L2(TT, 0); else if (op == 1) L2(TT, 1); else if (op == 2) L2(TT, 2); else L2(TT, 3); } while (0)
-        if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
-#undef L2
+        dispatch_dtype(dtype, "elementwise", [&](auto t) {
+            using T = LMX_T(t);
+            const auto kern = op == 0 ? ew_kernel<T, 0> : op == 1 ? ew_kernel<T, 1> : op == 2 ? ew_kernel<T, 2> : ew_kernel<T, 3>;
+            hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, (const T*)a2, (const T*)b2, (T*)o2, rest);
+        });
     }
     LMX_CHECK_HIP(hipGetLastError());
 }
 
 void launch_cast_f32(int dtype, const float* src, void* dst, size_t n, hipStream_t st) {
     if (!n) return;
-#define L(TT) hipLaunchKernelGGL(cast_f32_kernel<TT>, dim3((unsigned)cdiv64((int64_t)n, 256)), dim3(256), 0, st, src, (TT*)dst, n)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "cast_f32", [&](auto t) {
+        hipLaunchKernelGGL(cast_f32_kernel<LMX_T(t)>, dim3((unsigned)cdiv64((int64_t)n, 256)), dim3(256), 0, st, src, (LMX_T(t)*)dst, n);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -738,9 +738,9 @@ __global__ __launch_bounds__(256) void col_sum_kernel(const T* __restrict__ dy, 
 }
 void launch_col_sum(int dtype, const void* dy, int ld, int rows, int cols, float* out, hipStream_t st) {
     if (cols <= 0) return;
-#define L(TT) hipLaunchKernelGGL(col_sum_kernel<TT>, dim3(cdiv(cols, 256)), dim3(256), 0, st, (const TT*)dy, ld, rows, cols, out)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "col_sum", [&](auto t) {
+        hipLaunchKernelGGL(col_sum_kernel<LMX_T(t)>, dim3(cdiv(cols, 256)), dim3(256), 0, st, (const LMX_T(t)*)dy, ld, rows, cols, out);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -756,9 +756,9 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const int* __restrict__ 
 }
 void launch_embed_bwd(int dtype, const int* src, const void* d, float* dtable, void* dfeats, int rows, int H, hipStream_t st) {
     if (rows <= 0) return;
-#define L(TT) hipLaunchKernelGGL(embed_bwd_kernel<TT>, dim3(rows), dim3(256), 0, st, src, (const TT*)d, dtable, (TT*)dfeats, H)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "embed_bwd", [&](auto t) {
+        hipLaunchKernelGGL(embed_bwd_kernel<LMX_T(t)>, dim3(rows), dim3(256), 0, st, src, (const LMX_T(t)*)d, dtable, (LMX_T(t)*)dfeats, H);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -781,9 +781,9 @@ void launch_sumsq(int dtype, const void* x, size_t n, float* acc, hipStream_t st
     if (!n) return;
     LMX_REQUIRE(reinterpret_cast<uintptr_t>(x) % 16 == 0, "sumsq: x must be 16-byte aligned");
     const unsigned grid = (unsigned)std::min<int64_t>(cdiv64((int64_t)n, 256 * 8 * 4), 4096);
-#define L(TT) hipLaunchKernelGGL(sumsq_kernel<TT>, dim3(grid), dim3(256), 0, st, (const TT*)x, n, acc)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "sumsq", [&](auto t) {
+        hipLaunchKernelGGL(sumsq_kernel<LMX_T(t)>, dim3(grid), dim3(256), 0, st, (const LMX_T(t)*)x, n, acc);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
@@ -814,10 +814,10 @@ void launch_adamw(int dtype, void* param, const void* grad, float* master, float
     if (!n) return;
     LMX_REQUIRE(step >= 1, "adamw: step counts from 1");
     const float bc1 = 1.f - powf(b1, (float)step), bc2_sqrt = sqrtf(1.f - powf(b2, (float)step));
-#define L(TT) hipLaunchKernelGGL(adamw_kernel<TT>, dim3((unsigned)cdiv64((int64_t)n, 256)), dim3(256), 0, st, (TT*)param, (const TT*)grad, master, m, v, n, lr, b1, b2, \
-                                 eps, wd, bc1, bc2_sqrt, gnorm_sq, max_norm)
-    if (dtype == kBF16) L(bf16_t); else if (dtype == kF16) L(f16_t); else L(float);
-#undef L
+    dispatch_dtype(dtype, "adamw", [&](auto t) {
+        hipLaunchKernelGGL(adamw_kernel<LMX_T(t)>, dim3((unsigned)cdiv64((int64_t)n, 256)), dim3(256), 0, st, (LMX_T(t)*)param, (const LMX_T(t)*)grad, master, m, v, n, lr, b1, b2,
+                           eps, wd, bc1, bc2_sqrt, gnorm_sq, max_norm);
+    });
     LMX_CHECK_HIP(hipGetLastError());
 }
 
