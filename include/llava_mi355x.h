@@ -203,6 +203,22 @@ int lmx_seq_set_sampling(lmx_seq* s, float temperature, float top_p, int32_t top
 int lmx_seq_set_stop(lmx_seq* s, const int64_t* eos_ids, int32_t n_eos, const int64_t* kw_flat, const int32_t* kw_lens, int32_t n_kw, void* stream);
 /* out = 1 once the sequence's stop rule has fired (synchronises `stream`) */
 int lmx_seq_stopped(lmx_seq* s, int32_t* out, void* stream);
+/* replaces: the logits processors HF's generate() runs on the HOST between lm_head and the pick (`_get_logits_processor`: repetition_penalty,
+ * no_repeat_ngram_size, min_new_tokens / min_length, suppress_tokens, single-id bad_words_ids).  Here they live with the sequence on the device: every pick of
+ * lmx_prefill / lmx_prefill_batch / lmx_decode / lmx_decode_batch for this sequence — argmax or draw — sees the last position's logits, converted to fp32,
+ * after these rules in HF's order; the logits row in memory (logits_dev of lmx_prefill / lmx_decode) stays raw.
+ *   history h = prompt_ids_host[0, n_prompt) (the row's input_ids as passed to generate(): image markers and padding stay in) ++ the generated ids
+ *   repetition_penalty p (0 or 1 = off): every distinct id t of h gets l_t = l_t < 0 ? l_t * p : l_t / p   (a true division)
+ *   no_repeat_ngram n (0 = off): if |h| + 1 >= n, every id that would complete an n-gram already in h is banned (NoRepeatNGramLogitsProcessor)
+ *   min_new_tokens: the eos_ids (up to 4) are banned while fewer ids than that have been generated
+ *   suppress_ids (up to 16): always banned
+ * Banned = -inf; a row with every id banned picks 0.  Ids of h, eos_ids and suppress_ids outside [0, vocabulary) take no part — the image marker -200 among
+ * them: a stated deviation, HF's gather raises on it.  The prompt ids are copied (through pinned staging) into a per-sequence device buffer that holds
+ * max_position + 8 ids; the call is ordered on `stream` and does not drain it.  All-neutral values clear the rules, as do lmx_seq_reset, lmx_seq_truncate
+ * and the sequence's return to the pool.  Fails if n_prompt exceeds that buffer, a count exceeds its cap, or the vocabulary exceeds 196608 ids (the rules'
+ * two bitmaps live in LDS).  Call before lmx_prefill so that the prefill's own pick (token 1) follows the rules too. */
+int lmx_seq_set_logit_rules(lmx_seq* s, float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens, const int64_t* eos_ids, int32_t n_eos,
+                            const int64_t* suppress_ids, int32_t n_suppress, const int64_t* prompt_ids_host, int32_t n_prompt, void* stream);
 
 /* ---- decode batch: continuous batching --------------------------------------------------------------
  * new in this build: the reference serves up to --limit-model-concurrency requests as independent generate() threads with no
@@ -301,6 +317,13 @@ size_t lmx_op_decode_attn_batch_tab_bytes(int32_t n_seq);
 size_t lmx_op_decode_attn_ws_bytes(int32_t n_rows, int32_t n_heads, int32_t n_split, int32_t head_dim);
 int lmx_op_sample(int32_t dtype, const void* logits_dev, int32_t V, float temperature, float top_p, int32_t top_k, uint64_t seed,
                   const int32_t* offset_dev, const uint32_t* u32_override_host, int64_t* out_tok_dev, uint8_t* keep_out_dev, void* stream);
+/* The ruled pick on a caller-supplied row and history (the device code lmx_seq_set_logit_rules switches on; stands to it as lmx_op_sample stands to the
+ * sampler).  logits_dev: one row of V ids inside a buffer of ld >= V elements; history_dev: n_hist ids (device) of which the last n_out are generated ones;
+ * temperature <= 0: argmax, else a draw (u32_override_host as in lmx_op_sample).  processed_row_dev ([V] fp32) / keep_out_dev ([V]) may be NULL. */
+int lmx_op_pick_rules(int32_t dtype, const void* logits_dev, int32_t V, int32_t ld, const int64_t* history_dev, int32_t n_hist, int32_t n_out,
+                      float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens, const int64_t* eos_ids, int32_t n_eos,
+                      const int64_t* suppress_ids, int32_t n_suppress, float temperature, float top_p, int32_t top_k, uint64_t seed,
+                      const uint32_t* u32_override_host, int64_t* out_tok_dev, float* processed_row_dev, uint8_t* keep_out_dev, void* stream);
 int lmx_op_argmax(int32_t dtype, const void* logits, int32_t V, int64_t* out_tok_dev, void* stream);
 int lmx_op_im2col(int32_t dtype, const void* pixels, void* out, int32_t N, int32_t S, int32_t patch, int32_t kpad, void* stream);
 
@@ -380,7 +403,7 @@ int lmx_seq_copy(lmx_seq* dst, const lmx_seq* src, void* stream);
  *   lmx_op_hash128     128-bit content hash of `items` device buffers of bytes_per_item bytes each (out_dev[2 * item + {0, 1}], 16 bytes per item): the key of
  *                      the host mirror's image-feature cache (encode_images of pixels already seen returns the stored rows)
  *   lmx_seq_truncate   keep the K / V^T rows of positions [0, n_rows) of a finished request's sequence and forget the rest of that request (position, token
- *                      log, sampling parameters, stop rule): the next request, whose spliced prompt shares those rows, prefills only what follows them */
+ *                      log, sampling parameters, stop rule, logits processors): the next request, whose spliced prompt shares those rows, prefills only what follows them */
 int lmx_op_hash128(const void* base_dev, uint64_t bytes_per_item, int32_t items, uint64_t* out_dev, void* stream);
 int lmx_seq_truncate(lmx_seq* s, int32_t n_rows, void* stream);
 /* Packed prefill of several requests (serving; the reference prefills each request alone inside its own generate() thread, model_worker.py:174-185):

@@ -199,6 +199,7 @@ int lmx_seq_create(lmx_model* m, lmx_seq** out) {
         if (s->impl.ev_idle) LMX_CHECK_HIP(hipEventSynchronize(s->impl.ev_idle));
         s->impl.len = 0;
         s->impl.samp = SampleParams{};
+        s->impl.clear_logit_rules();
         s->impl.uid = next_seq_uid();
         zero_fill(s->impl.state.p, 16);
         zero_fill(s->impl.stopbuf.p, sizeof(StopSpec));
@@ -214,6 +215,7 @@ int lmx_seq_destroy(lmx_seq* s) {
     if (!s) return 0;
     Model* m = s->impl.m;
     if (m) m->live_seqs.fetch_sub(1, std::memory_order_relaxed);
+    s->impl.clear_logit_rules();          // a pooled sequence carries no request's logits processors
     bool pooled = false;
     bool idle_known = true;
     if (m && s->impl.used) {
@@ -277,6 +279,41 @@ int lmx_seq_set_sampling(lmx_seq* s, float temperature, float top_p, int32_t top
     s->impl.uid = next_seq_uid();          // a decode batch holding this sequence rebuilds its table entry
     LMX_API_END
 }
+static LogitRules make_rules(float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens, const int64_t* eos_ids, int32_t n_eos,
+                             const int64_t* suppress_ids, int32_t n_suppress, int32_t n_prompt) {
+    LMX_REQUIRE(repetition_penalty >= 0.f, "logit rules: repetition_penalty must be positive (0 or 1 = off)");
+    LMX_REQUIRE(no_repeat_ngram >= 0 && min_new_tokens >= 0, "logit rules: no_repeat_ngram and min_new_tokens must be >= 0 (0 = off)");
+    LMX_REQUIRE(n_eos >= 0 && n_eos <= RULES_MAX_EOS && (n_eos == 0 || eos_ids), "logit rules: at most 4 end-of-sequence ids");
+    LMX_REQUIRE(n_suppress >= 0 && n_suppress <= RULES_MAX_SUPPRESS && (n_suppress == 0 || suppress_ids), "logit rules: at most 16 suppressed ids");
+    LMX_REQUIRE(n_prompt >= 0, "logit rules: negative history length");
+    LogitRules r{};
+    r.penalty = repetition_penalty; r.ngram = no_repeat_ngram; r.min_new = min_new_tokens; r.n_eos = n_eos; r.n_suppress = n_suppress; r.n_prompt = n_prompt;
+    for (int i = 0; i < n_eos; ++i) r.eos[i] = eos_ids[i];
+    for (int i = 0; i < n_suppress; ++i) r.suppress[i] = suppress_ids[i];
+    return r;
+}
+int lmx_seq_set_logit_rules(lmx_seq* s, float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens, const int64_t* eos_ids, int32_t n_eos,
+                            const int64_t* suppress_ids, int32_t n_suppress, const int64_t* prompt_ids_host, int32_t n_prompt, void* stream) {
+    LMX_API_BEGIN
+    LMX_REQUIRE(s, "null sequence");
+    s->impl.set_logit_rules(make_rules(repetition_penalty, no_repeat_ngram, min_new_tokens, eos_ids, n_eos, suppress_ids, n_suppress, n_prompt), prompt_ids_host,
+                            S(stream));
+    LMX_API_END
+}
+int lmx_op_pick_rules(int32_t dtype, const void* logits_dev, int32_t V, int32_t ld, const int64_t* history_dev, int32_t n_hist, int32_t n_out,
+                      float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens, const int64_t* eos_ids, int32_t n_eos,
+                      const int64_t* suppress_ids, int32_t n_suppress, float temperature, float top_p, int32_t top_k, uint64_t seed,
+                      const uint32_t* u32_override_host, int64_t* out_tok_dev, float* processed_row_dev, uint8_t* keep_out_dev, void* stream) {
+    LMX_API_BEGIN
+    LMX_REQUIRE(logits_dev && out_tok_dev && V > 0 && ld >= V, "pick_rules: null argument or row pitch below V");
+    LMX_REQUIRE(n_hist == 0 || history_dev, "pick_rules: null history");
+    LMX_REQUIRE(n_out >= 0 && n_out <= n_hist, "pick_rules: n_out counts the generated ids at the end of the history");
+    LogitRules r = make_rules(repetition_penalty, no_repeat_ngram, min_new_tokens, eos_ids, n_eos, suppress_ids, n_suppress, n_hist);
+    r.prompt = history_dev;
+    launch_pick_rules(dtype, logits_dev, V, r, nullptr, 0, nullptr, n_out, SampleParams{temperature > 0.f ? temperature : 0.f, top_p, top_k, (uint32_t)seed, (uint32_t)(seed >> 32)},
+                      u32_override_host, out_tok_dev, processed_row_dev, keep_out_dev, S(stream));
+    LMX_API_END
+}
 int lmx_op_sample(int32_t dtype, const void* logits_dev, int32_t V, float temperature, float top_p, int32_t top_k, uint64_t seed,
                   const int32_t* offset_dev, const uint32_t* u32_override_host, int64_t* out_tok_dev, uint8_t* keep_out_dev, void* stream) {
     LMX_API_BEGIN
@@ -290,6 +327,7 @@ int lmx_seq_reset(lmx_seq* s) {
     s->impl.len = 0;
     zero_fill(s->impl.state.p, 16);       // caller guarantees no work on this sequence is in flight
     zero_fill(&s->impl.d_stop->done, sizeof(int));      // a sequence that stopped by its id rule is live again (the rule itself stays until the next set_stop)
+    s->impl.clear_logit_rules();                        // the logits processors belong to the request that set them
     LMX_API_END
 }
 int lmx_seq_length(const lmx_seq* s) { return s ? s->impl.len : -1; }
@@ -707,6 +745,7 @@ int lmx_seq_truncate(lmx_seq* s, int32_t n_rows, void* stream) {
     // rest of the request — position, token log, sampling parameters, stop rule (ordered on `stream` behind whatever still runs on the sequence)
     s->impl.len = n_rows;
     s->impl.samp = SampleParams{};
+    s->impl.clear_logit_rules();
     s->impl.uid = next_seq_uid();
     s->impl.last_stream = S(stream); s->impl.used = true;
     launch_set_state(s->impl.d_len, n_rows, s->impl.d_tok, 0, 1, s->impl.d_nout, 0, S(stream));

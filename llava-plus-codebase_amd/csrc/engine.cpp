@@ -541,7 +541,36 @@ Seq::Seq(Model* mm) : m(mm) {
     LMX_CHECK_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_status), h_status, 0));
 }
 
+// The rule values travel as a kernel argument; the prompt ids are copied into pinned memory here and from there to the device on `st`, so the caller's
+// buffer is free on return and nothing waits for the stream (only a second setter call on the same sequence waits for the first one's copy).
+void Seq::set_logit_rules(const LogitRules& r, const int64_t* prompt_host, hipStream_t st) {
+    if (logit_rules_neutral(r)) { clear_logit_rules(); return; }
+    LMX_REQUIRE(r.n_prompt >= 0 && r.n_prompt <= log_cap, "set_logit_rules: more prompt ids than the sequence's token log holds (max_position + 8)");
+    LMX_REQUIRE(r.n_prompt == 0 || prompt_host, "set_logit_rules: null prompt ids");
+    LMX_REQUIRE(m->Vr <= RULES_MAX_V, "set_logit_rules: the vocabulary is too large for the logits-processor bitmaps (196608 ids)");
+    // First use allocates; each resource is tested on its own, so a call that failed half way leaves nothing the next call would use unallocated.
+    // No zero fill: the kernels read promptbuf[0, n_prompt) only, and rulesbuf only after launch_set_logit_rules below has written it.
+    if (ev_prompt) { LMX_CHECK_HIP(hipEventSynchronize(ev_prompt)); }          // the previous call's copy has left the staging buffer
+    else { LMX_CHECK_HIP(hipEventCreateWithFlags(&ev_prompt, hipEventDisableTiming)); }
+    if (!h_prompt) { LMX_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_prompt), (size_t)log_cap * sizeof(int64_t), hipHostMallocDefault)); }
+    rulesbuf.ensure(sizeof(LogitRules));
+    promptbuf.ensure((size_t)log_cap * sizeof(int64_t));
+    if (r.n_prompt > 0) {
+        std::memcpy(h_prompt, prompt_host, (size_t)r.n_prompt * sizeof(int64_t));
+        LMX_CHECK_HIP(hipMemcpyAsync(promptbuf.p, h_prompt, (size_t)r.n_prompt * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    }
+    LMX_CHECK_HIP(hipEventRecord(ev_prompt, st));
+    rules = r;
+    rules.prompt = promptbuf.as<int64_t>();
+    launch_set_logit_rules(rulesbuf.as<LogitRules>(), rules, st);
+    rules_on = true;
+    last_stream = st; used = true;
+    uid = next_seq_uid();          // a decode batch holding this sequence rebuilds its table entry
+}
+
 Seq::~Seq() {
+    if (h_prompt) (void)hipHostFree(h_prompt);
+    if (ev_prompt) (void)hipEventDestroy(ev_prompt);
     if (h_status) (void)hipHostFree(h_status);
     if (ev_idle) (void)hipEventDestroy(ev_idle);
     for (int i = 0; i < 2; ++i) { if (ev_c[i]) (void)hipEventDestroy(ev_c[i]); if (ev_r[i]) (void)hipEventDestroy(ev_r[i]); }
@@ -673,7 +702,9 @@ void Model::prefill_head(Seq* s, const void* h_row, void* dst, bool pick, hipStr
     { LMX_PROF_K("prefill.gemv.lm_head"); launch_gemv(dt, GemvArgs{h_row, lm_head, static_cast<char*>(dst) + (size_t)v_off * es, nullptr, nullptr, final_norm, cfg.rms_eps, V_l, H, H, H, V, 0, kActNone}, 1, st); }
     gather_logits(dst, 1, st);
     if (!pick) return;
-    if (s->samp.temperature > 0.f) launch_sample(dt, dst, Vr, s->samp, s->d_nout, s->d_tok, nullptr, nullptr, st);
+    // with logits processors: the ruled pick (history = the prompt ids + whatever the log holds: nothing, for a request's first token)
+    if (s->rules_on) launch_pick_rules(dt, dst, Vr, s->rules, s->d_log, s->log_cap, s->d_nout, 0, s->samp, nullptr, s->d_tok, nullptr, nullptr, st);
+    else if (s->samp.temperature > 0.f) launch_sample(dt, dst, Vr, s->samp, s->d_nout, s->d_tok, nullptr, nullptr, st);
     else launch_argmax(dt, dst, Vr, s->d_tok, st);
     launch_log_token(s->d_tok, s->d_log, s->d_nout, s->log_cap, s->d_stop, st);
 }
@@ -817,8 +848,8 @@ void Model::decode_step_launch(Seq* s, hipStream_t st, int64_t* id_out) {
     { ProfScope ps_ag(this, V_l != V ? "decode.allgather.logits" : nullptr, st); gather_logits(s->d_logits, 1, st); }
     {
         LMX_PROF("decode.argmax");      // pick (argmax | draw) + *len += 1 + token log + next token's embedding row -> d_h, one launch
-        const SeqStateRef r{s->d_len, s->d_nout, s->d_tok, s->d_log, s->log_cap, 0, s->samp, s->d_stop};
-        launch_argmax_advance_batch(dt, s->d_logits, Vr, V, nullptr, &r, 1, id_out, embed, s->d_h, H, st);      // id_out: the picked id, or -1 once the stop rule has fired
+        const SeqStateRef r = s->state_ref();
+        launch_argmax_advance_batch(dt, s->d_logits, Vr, V, nullptr, &r, 1, id_out, embed, s->d_h, H, st, s->rules_on);      // id_out: the picked id, or -1 once the stop rule has fired
     }
 }
 
@@ -915,7 +946,7 @@ void Batch::bind(Seq* const* seqs, int n, hipStream_t st) {
         for (int l = 0; l < L; ++l)
             at[(size_t)l * cap + i] = DecodeFusedSeq{s->kc.as<char>() + (size_t)l * s->layer_stride, s->vt.as<char>() + (size_t)l * s->layer_stride,
                                                      s->d_len, s->d_aws, s->d_cnt};
-        stt[i] = SeqStateRef{s->d_len, s->d_nout, s->d_tok, s->d_log, s->log_cap, 0, s->samp, s->d_stop};
+        stt[i] = s->state_ref();
     }
     // the previous step's kernels may still be reading the old tables on this stream, and the host image is reused
     LMX_CHECK_HIP(hipStreamSynchronize(st));
@@ -942,6 +973,8 @@ void Model::decode_batch(Batch* b, Seq* const* seqs, int n, const int64_t* token
     }
     if (n > 1) ensure_batch_weights(st);
     b->bind(seqs, n, st);
+    bool any_rules = false;        // per launch: the rules-carrying pick only when some member has logits processors
+    for (int i = 0; i < n; ++i) any_rules = any_rules || seqs[i]->rules_on;
     if (n_steps > b->ids_steps) { LMX_CHECK_HIP(hipStreamSynchronize(st)); b->ids.ensure((size_t)n_steps * b->cap * 8); b->ids_steps = n_steps; }
     int64_t* d_ids = b->ids.as<int64_t>();
     if (tokens)
@@ -998,7 +1031,7 @@ void Model::decode_batch(Batch* b, Seq* const* seqs, int n, const int64_t* token
         linear(x_ready ? b->x : b->h, x_ready ? nullptr : final_norm, b->x, GemmArgs{x_ready ? b->x : b->h, lm_head, static_cast<char*>(b->logits) + (size_t)v_off * es, nullptr, nullptr, n, V_l, H, H, H, V, 0, kActNone}, sw_lm_head);
         gather_logits(b->logits, n, st);
         // pick + advance + the picked tokens' embedding rows -> b->h (input of the next step), one launch
-        { LMX_PROF("decode_batch.argmax"); launch_argmax_advance_batch(dt, b->logits, Vr, V, b->d_state_tab, nullptr, n, d_ids + (size_t)step * b->cap, embed, b->h, H, st); }
+        { LMX_PROF("decode_batch.argmax"); launch_argmax_advance_batch(dt, b->logits, Vr, V, b->d_state_tab, nullptr, n, d_ids + (size_t)step * b->cap, embed, b->h, H, st, any_rules); }
         for (int i = 0; i < n; ++i) seqs[i]->len += 1;
     }
     }

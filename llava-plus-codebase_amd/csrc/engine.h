@@ -55,6 +55,7 @@ struct VisLayerW {
 };
 
 struct Seq;
+uint64_t next_seq_uid();
 
 struct Model {
     lmx_config cfg{};
@@ -195,6 +196,15 @@ struct Seq {
     int* d_len = nullptr; int* d_nout = nullptr; int64_t* d_tok = nullptr; int64_t* d_log = nullptr;
     DevBuf stopbuf; StopSpec* d_stop = nullptr;          // device-side stop rule (lmx_seq_set_stop); all zero = no rule
     int log_cap = 0;
+    // device-side logits processors (lmx_seq_set_logit_rules; kernels.h: LogitRules).  rules_on = the host's copy `rules` is non-neutral: only then do the
+    // picks of this sequence take the rules-carrying kernels.  The prompt ids live in promptbuf (capacity log_cap ids), staged through pinned host memory
+    // so that the setter's copy is ordered on the caller's stream without draining it; all three are allocated by the first setter call.
+    LogitRules rules{}; bool rules_on = false;
+    DevBuf rulesbuf, promptbuf; int64_t* h_prompt = nullptr; hipEvent_t ev_prompt = nullptr;
+    const LogitRules* d_rules() const { return rules_on ? rulesbuf.as<LogitRules>() : nullptr; }
+    void set_logit_rules(const LogitRules& r, const int64_t* prompt_host, hipStream_t st);      // r.prompt is ignored: the ids come from prompt_host
+    void clear_logit_rules() { if (rules_on) { rules_on = false; rules = LogitRules{}; uid = next_seq_uid(); } }
+    SeqStateRef state_ref() const { return SeqStateRef{d_len, d_nout, d_tok, d_log, log_cap, 0, samp, d_stop, d_rules()}; }
     DevBuf pws;                        // prefill workspace
     DevBuf skw;                        // split-K partial tiles of the ping-pong GEMM (o_proj, down_proj of a prefill)
     DevBuf dws;                        // decode workspace

@@ -234,7 +234,22 @@ struct SampleParams { float temperature = 0.f; float top_p = 1.f; int top_k = 0;
 // batch still running — produce nothing past the stop and the host needs no per-token round trip to know where it was.
 constexpr int STOP_MAX_EOS = 4, STOP_MAX_KW = 4, STOP_MAX_KW_LEN = 8;
 struct StopSpec { int done; int n_eos; int n_kw; int pad; int64_t eos[STOP_MAX_EOS]; int kw_len[STOP_MAX_KW]; int64_t kw[STOP_MAX_KW][STOP_MAX_KW_LEN]; };
-struct SeqStateRef { int* len; int* n_out; int64_t* tok; int64_t* log; int log_cap; int pad; SampleParams sample; StopSpec* stop; };
+// device-side logits processors of a sequence (lmx_seq_set_logit_rules): HF's RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor,
+// MinNewTokensLengthLogitsProcessor and SuppressTokensLogitsProcessor (in _get_logits_processor's order), applied by the pick itself to the logits it
+// loads — the row in memory stays raw.  The history h = prompt[0, n_prompt) ++ log[0, n_out): the row's input_ids as passed to generate() (image markers and
+// padding included), then the generated ids.  Ids outside [0, V) take no part (HF cannot run these processors on an image prompt at all: gather raises
+// on -200).  penalty 0 or 1 = off, ngram 0 = off.  A null pointer or an all-zero struct is "no rule".
+constexpr int RULES_MAX_EOS = 4, RULES_MAX_SUPPRESS = 16;
+constexpr int RULES_MAX_V = 196608;      // the two [0, V) bitmaps (seen | ban) live in LDS beside the sampler's scratch: 2 x 24 KB at most
+struct LogitRules {
+    float penalty; int ngram; int min_new; int n_eos; int n_suppress; int n_prompt;
+    const int64_t* prompt;
+    int64_t eos[RULES_MAX_EOS]; int64_t suppress[RULES_MAX_SUPPRESS];
+};
+__host__ __device__ inline bool logit_rules_neutral(const LogitRules& r) {
+    return (r.penalty == 0.f || r.penalty == 1.f) && r.ngram <= 0 && (r.min_new <= 0 || r.n_eos <= 0) && r.n_suppress <= 0;
+}
+struct SeqStateRef { int* len; int* n_out; int64_t* tok; int64_t* log; int log_cap; int pad; SampleParams sample; StopSpec* stop; const LogitRules* rules = nullptr; };
 // the two id rules on a sequence whose n_after generated ids (the last one = t) sit in log[0 .. n_after): t is an EOS id | the last len(kw) ids equal kw
 __device__ __forceinline__ bool stop_rule_fires(const StopSpec* sp, int64_t t, const int64_t* log, int n_after, int log_cap) {
     bool hit = false;
@@ -255,8 +270,18 @@ void launch_gather_tokens_batch(int dtype, const SeqStateRef* tab, int n, const 
 // V = ids considered (the real vocabulary), ld = row pitch of `logits` (the padded vocabulary)
 // then (embed != null) h_out[i] = embed[tok]: the next step's input row.  State comes from the device table `tab` (n members)
 // or from `single` (host pointer, passed by value; n must be 1).
+// rules: some member carries LogitRules — the launch takes the rules-carrying instantiation (members without rules skip the bitmap build inside it);
+// false = the plain instantiation, which never looks at SeqStateRef::rules
 void launch_argmax_advance_batch(int dtype, const void* logits, int V, int ld, const SeqStateRef* tab, const SeqStateRef* single, int n, int64_t* ids_out,
-                                 const void* embed, void* h_out, int H, hipStream_t st);
+                                 const void* embed, void* h_out, int H, hipStream_t st, bool rules = false);
+// *dst = v on the stream (v travels as a kernel argument, like the stop rule)
+void launch_set_logit_rules(LogitRules* dst, const LogitRules& v, hipStream_t st);
+// The ruled pick alone, without the advance: *out_tok = argmax (p.temperature <= 0) or a draw of the PROCESSED row.  n_out = *n_out_ptr when given, else the
+// value; the history is rules.prompt[0, n_prompt) ++ log[0, n_out) (log may be null: the history is then rules.prompt alone and n_out only feeds the
+// min-new-tokens rule and the Philox offset).  `rules` is a host struct whose `prompt` is a device pointer.  Optional outputs: processed [V] fp32 (the row
+// after the rules), keep_out [V] (survivors of a draw).  The prefill's first pick runs this; lmx_op_pick_rules exposes it to the tests.
+void launch_pick_rules(int dtype, const void* logits, int V, const LogitRules& rules, const int64_t* log, int log_cap, const int* n_out_ptr, int n_out,
+                       const SampleParams& p, const uint32_t* u32_override, int64_t* out_tok, float* processed, uint8_t* keep_out, hipStream_t st);
 
 // ---- one-shot peer-to-peer all-reduce for decode-sized messages (p2p.hip) ---------------------------------------------
 constexpr int P2P_MAX_ROWS = 32;     // rows ([H] each) per launch = largest decode batch that goes through the skinny path

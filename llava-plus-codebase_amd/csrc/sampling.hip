@@ -61,6 +61,86 @@ __device__ __forceinline__ uint64_t block_sum_u64_1024(uint64_t v, uint64_t* red
     return s;
 }
 
+// ---- logits processors inside the pick (kernels.h: LogitRules) -----------------------------------------------------------------------------------
+// The rules-carrying instantiations (template flag RULES) build two bitmaps over [0, V) in dynamic LDS at entry — `seen`: ids of the history (repetition
+// penalty), `ban`: ids that must not be picked (no-repeat n-gram, EOS below min_new, suppress) — and every logit they load goes through adjust(): the row is
+// processed on the way into registers, with no second pass over it, no extra launch, and the row in memory stays raw.  Instantiations without the flag
+// carry an empty view and compile to the code they were before the rules existed.
+extern __shared__ uint32_t rule_bits[];      // RULES only: seen words [0, W), ban words [W, 2 W), W = ceil(V / 32)
+static size_t rule_bits_bytes(int V) { return (size_t)2 * ((V + 31) / 32) * sizeof(uint32_t); }
+
+template <bool RULES> struct RuleView {};
+template <> struct RuleView<true> { int W; float p; bool on, pen; };      // the bitmaps are addressed as rule_bits[w] / rule_bits[W + w]: LDS reads, no pointers to keep
+
+// HF order: RepetitionPenaltyLogitsProcessor (l < 0 ? l * p : l / p, a true division: fp32 rows match torch bit for bit), then the bans (-inf)
+template <bool RULES>
+__device__ __forceinline__ float adjust(const RuleView<RULES>& rv, int i, float v) {
+    if constexpr (RULES) {
+        if (!rv.on) return v;
+        const uint32_t w = (uint32_t)i >> 5, b = 1u << (i & 31);
+        if (rule_bits[rv.W + w] & b) return -INFINITY;
+        if (rv.pen && (rule_bits[w] & b)) return v < 0.f ? v * rv.p : __fdiv_rn(v, rv.p);
+    }
+    return v;
+}
+// eight consecutive ids from a multiple of 8 share one word of each bitmap: one LDS read per bitmap instead of eight, none of the arithmetic when the byte is clear
+template <bool RULES>
+__device__ __forceinline__ void adjust8(const RuleView<RULES>& rv, int i, float (&v)[8]) {
+    if constexpr (RULES) {
+        if (!rv.on) return;
+        const uint32_t w = (uint32_t)i >> 5, s = (uint32_t)i & 31u;
+        const uint32_t ban = (rule_bits[rv.W + w] >> s) & 0xFFu;
+        const uint32_t seen = rv.pen ? (rule_bits[w] >> s) & 0xFFu : 0u;
+        if ((ban | seen) == 0u) return;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if ((ban >> j) & 1u) v[j] = -INFINITY;
+            else if ((seen >> j) & 1u) v[j] = v[j] < 0.f ? v[j] * rv.p : __fdiv_rn(v[j], rv.p);
+        }
+    }
+}
+template <bool RULES>
+__device__ __forceinline__ bool rule_banned(const RuleView<RULES>& rv, int i) {
+    if constexpr (RULES) return rv.on && ((rule_bits[rv.W + ((uint32_t)i >> 5)] >> (i & 31)) & 1u) != 0u;
+    return false;
+}
+
+// Workgroup-wide (NT threads).  History h = lr.prompt[0, n_prompt) ++ log[0, n_log), len = |h|; ids outside [0, V) are skipped everywhere.
+//   seen : every id of h (one atomicOr per history id)
+//   ban  : no-repeat n-gram (NoRepeatNGramLogitsProcessor): if len + 1 >= n, for every start j with j + n - 1 <= len - 1 and h[j : j + n - 1] == the last
+//          n - 1 ids of h, the id h[j + n - 1] (n = 1: every id of h) — threads stride over j;  the EOS ids while n_out < min_new;  the suppress ids
+template <int NT>
+__device__ __forceinline__ RuleView<true> build_rule_bitmaps(const LogitRules& lr, const int64_t* __restrict__ log, int n_log, int n_out, int V) {
+    const int W = (V + 31) >> 5, tid = threadIdx.x;
+    uint32_t* seen = rule_bits;
+    uint32_t* ban = rule_bits + W;
+    for (int w = tid; w < 2 * W; w += NT) rule_bits[w] = 0u;
+    __syncthreads();
+    const int64_t* __restrict__ prompt = lr.prompt;
+    const int np = (prompt && lr.n_prompt > 0) ? lr.n_prompt : 0;
+    const int len = np + ((log && n_log > 0) ? n_log : 0);
+    auto hid = [&](int j) -> int64_t { return j < np ? prompt[j] : log[j - np]; };
+    auto mark = [&](uint32_t* bits, int64_t t) { if (t >= 0 && t < (int64_t)V) atomicOr(&bits[(uint32_t)t >> 5], 1u << ((uint32_t)t & 31u)); };
+    const bool pen = lr.penalty > 0.f && lr.penalty != 1.f;
+    if (pen) for (int j = tid; j < len; j += NT) mark(seen, hid(j));
+    const int n = lr.ngram;
+    if (n >= 1 && len + 1 >= n) {
+        const int m = n - 1, s0 = len - m;
+        for (int j = tid; j + m < len; j += NT) {
+            bool eq = true;
+            for (int k = 0; k < m && eq; ++k) eq = hid(j + k) == hid(s0 + k);
+            if (eq) mark(ban, hid(j + m));
+        }
+    }
+    const bool hold_eos = n_out < lr.min_new;
+#pragma unroll
+    for (int e = 0; e < RULES_MAX_EOS; ++e) if (hold_eos && tid == e && e < lr.n_eos) mark(ban, lr.eos[e]);
+#pragma unroll
+    for (int e = 0; e < RULES_MAX_SUPPRESS; ++e) if (tid == e && e < lr.n_suppress) mark(ban, lr.suppress[e]);
+    __syncthreads();
+    return RuleView<true>{W, lr.penalty, true, pen};
+}
+
 struct SampleScratch {
     float redf[16];
     uint64_t redu[16];
@@ -70,15 +150,15 @@ struct SampleScratch {
 };
 
 // Returns the sampled token id (valid in every thread).  keep_out (debug, may be null): 1 for every surviving token id.
-template <typename T>
+template <typename T, bool RULES = false>
 __device__ int64_t sample_row(const T* __restrict__ logits, int V, float temperature, float top_p, int top_k, uint32_t u32,
-                              SampleScratch& sh, uint8_t* __restrict__ keep_out) {
+                              SampleScratch& sh, uint8_t* __restrict__ keep_out, RuleView<RULES> rv = {}) {
     const int tid = threadIdx.x;
     const float inv_t = 1.f / fmaxf(temperature, 1e-5f);
     float mx = -INFINITY;
-    for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, to_f32(logits[i]));
+    for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, adjust(rv, i, to_f32(logits[i])));
     mx = block_max_1024(mx, sh.redf);
-    auto e_of = [&](int i) { return expf((to_f32(logits[i]) - mx) * inv_t); };
+    auto e_of = [&](int i) { return expf((adjust(rv, i, to_f32(logits[i])) - mx) * inv_t); };
     auto q_of = [&](float e) { return (uint64_t)(uint32_t)(e * 2147483648.f); };
 
     // ---- top-k: key of the k-th largest e ----------------------------------------------------------------------------------
@@ -142,7 +222,7 @@ __device__ int64_t sample_row(const T* __restrict__ logits, int V, float tempera
     const int i0 = tid * C, i1 = (i0 + C < V) ? i0 + C : V;
     uint64_t mine = 0;
     for (int i = i0; i < i1; ++i) { const float e = e_of(i); if (__float_as_uint(e) >= thr_key) mine += q_of(e); }
-    if (keep_out) for (int i = i0; i < i1; ++i) keep_out[i] = __float_as_uint(e_of(i)) >= thr_key ? 1 : 0;
+    if (keep_out) for (int i = i0; i < i1; ++i) keep_out[i] = (__float_as_uint(e_of(i)) >= thr_key && !rule_banned(rv, i)) ? 1 : 0;
     sh.scan[tid] = mine;
     __syncthreads();
     for (int off = 1; off < 1024; off <<= 1) {               // inclusive Hillis-Steele scan of the 1024 chunk masses
@@ -299,11 +379,13 @@ __device__ int64_t sample_row_cached(const T* __restrict__ logits, int V, float 
 union SampleShared { SampleScratch generic; FastScratch fast; };
 
 // CPT = elements per thread of the register-cached path (host picks the smallest that covers V), 0 = generic streaming path
-template <typename T, int CPT>
+// The rules-carrying picks draw with the streaming path at every V (CPT = 0): the register-cached path fills the 128 VGPRs a 1024-thread workgroup has
+// (2 x 32 cached words per thread + the scan), and with the bitmap lookups beside them it spilled (16 - 68 bytes of scratch per lane, measured at compile time).
+template <typename T, int CPT, bool RULES = false>
 __device__ __forceinline__ int64_t sample_any(const T* logits, int V, float temperature, float top_p, int top_k, uint32_t u, SampleShared& sh,
-                                              uint8_t* keep_out) {
+                                              uint8_t* keep_out, RuleView<RULES> rv = {}) {
     if constexpr (CPT > 0) return sample_row_cached<T, CPT>(logits, V, temperature, top_p, top_k, u, sh.fast, keep_out);
-    else return sample_row<T>(logits, V, temperature, top_p, top_k, u, sh.generic, keep_out);
+    else return sample_row<T, RULES>(logits, V, temperature, top_p, top_k, u, sh.generic, keep_out, rv);
 }
 static int sample_cpt(int V) { return V <= FAST_NT * 32 ? 32 : 0; }
 
@@ -329,16 +411,51 @@ void launch_sample(int dtype, const void* logits, int V, const SampleParams& p, 
     LMX_CHECK_HIP(hipGetLastError());
 }
 
+// greedy pick of one row by an NT-thread workgroup: first index wins ties (torch.argmax), 0 when nothing is finite; valid in every thread
+template <typename T, int NT, bool RULES>
+__device__ __forceinline__ int64_t argmax_row(const T* __restrict__ logits, int V, float* bv, int* bi, RuleView<RULES> rv) {
+    float best = -INFINITY; int idx = 0x7fffffff;
+    const int V8 = V & ~7;
+    for (int i = threadIdx.x * 8; i < V8; i += NT * 8) {            // 16-byte loads; ascending ids inside a thread keep "first wins"
+        float v[8]; load8<T>(logits + i, v);
+        adjust8(rv, i, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) if (v[j] > best) { best = v[j]; idx = i + j; }
+    }
+    bool tie = true;                // a member without rules keeps the plain pick's tail loop, inside a rules-carrying launch too
+    if constexpr (RULES) tie = !rv.on;
+    for (int i = V8 + threadIdx.x; i < V; i += NT) {
+        const float v = adjust(rv, i, to_f32(logits[i]));
+        // (the tie clause never decides among finite values — a thread's ids ascend — but lets a -inf id displace the "nothing yet" index; with rules a row can
+        // be banned altogether and must then pick 0, as torch.argmax does)
+        if (v > best || (tie && v == best && i < idx)) { best = v; idx = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { bv[w] = best; bi[w] = idx; }
+    __syncthreads();
+    for (int i = 0; i < NT / 64; ++i)
+        if (bv[i] > best || (bv[i] == best && bi[i] < idx)) { best = bv[i]; idx = bi[i]; }
+    return idx == 0x7fffffff ? 0 : idx;
+}
+
 // End of a decode step, one workgroup per sequence: pick the next token (greedy argmax or a draw), advance the sequence state
 // (*len += 1, token log) and fetch the picked token's embedding row into the residual-stream row of the NEXT step — one launch
 // instead of argmax + advance + embedding gather.  `tab` (decode batch) or `single` (one sequence, by value) describes the state.
-template <typename T, int CPT>
+// RULES: the launch carries logits processors (some member has SeqStateRef::rules); a member without them only skips the bitmap build.
+template <typename T, int CPT, bool RULES = false>
 __global__ __launch_bounds__(CPT > 0 ? FAST_NT : 1024) void pick_advance_batch_kernel(const T* __restrict__ logits_all, int V, int ld, const SeqStateRef* __restrict__ tab,
                                                                   SeqStateRef single, int64_t* __restrict__ ids_out,
                                                                   const T* __restrict__ embed, T* __restrict__ h_out, int H) {
     __shared__ SampleShared sh;
     __shared__ float bv[16];
     __shared__ int bi[16];
+    constexpr int NT = CPT > 0 ? FAST_NT : 1024;
     const T* logits = logits_all + (size_t)blockIdx.x * ld;      // V = ids scanned (real vocabulary), ld = row pitch (padded)
     const SeqStateRef r = tab ? tab[blockIdx.x] : single;
     // stopped earlier (device-side stop rule): nothing of this sequence moves any more — workgroup-uniform, read before anyone could write it below
@@ -347,35 +464,23 @@ __global__ __launch_bounds__(CPT > 0 ? FAST_NT : 1024) void pick_advance_batch_k
         return;
     }
     __syncthreads();
+    RuleView<RULES> rv{};
+    if constexpr (RULES) {
+        rv.on = false;
+        if (r.rules) {                                          // workgroup-uniform
+            const LogitRules lr = *r.rules;
+            if (!logit_rules_neutral(lr)) {
+                const int n_out = *r.n_out;
+                rv = build_rule_bitmaps<NT>(lr, r.log, n_out < r.log_cap ? n_out : r.log_cap, n_out, V);
+            }
+        }
+    }
     int64_t t;
     if (r.sample.temperature > 0.f) {
         const uint32_t u = philox_u32(r.sample.seed_lo, r.sample.seed_hi, (uint32_t)*r.n_out);
-        t = sample_any<T, CPT>(logits, V, r.sample.temperature, r.sample.top_p, r.sample.top_k, u, sh, nullptr);
+        t = sample_any<T, CPT, RULES>(logits, V, r.sample.temperature, r.sample.top_p, r.sample.top_k, u, sh, nullptr, rv);
     } else {
-        float best = -INFINITY; int idx = 0x7fffffff;
-        constexpr int NT = CPT > 0 ? FAST_NT : 1024;
-        const int V8 = V & ~7;
-        for (int i = threadIdx.x * 8; i < V8; i += NT * 8) {            // 16-byte loads; ascending ids inside a thread keep "first wins"
-            float v[8]; load8<T>(logits + i, v);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) if (v[j] > best) { best = v[j]; idx = i + j; }
-        }
-        for (int i = V8 + threadIdx.x; i < V; i += NT) {
-            const float v = to_f32(logits[i]);
-            if (v > best || (v == best && i < idx)) { best = v; idx = i; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best, o, 64);
-            const int oi = __shfl_xor(idx, o, 64);
-            if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-        }
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        if (lane == 0) { bv[w] = best; bi[w] = idx; }
-        __syncthreads();
-        for (int i = 0; i < (CPT > 0 ? FAST_NT : 1024) / 64; ++i)
-            if (bv[i] > best || (bv[i] == best && bi[i] < idx)) { best = bv[i]; idx = bi[i]; }
-        t = idx == 0x7fffffff ? 0 : idx;
+        t = argmax_row<T, NT, RULES>(logits, V, bv, bi, rv);
     }
     if (threadIdx.x == 0) {
         *r.tok = t;
@@ -387,7 +492,6 @@ __global__ __launch_bounds__(CPT > 0 ? FAST_NT : 1024) void pick_advance_batch_k
         if (r.stop && stop_rule_fires(r.stop, t, r.log, n + 1, r.log_cap)) r.stop->done = 1;      // the reference's id rules on the sequence INCLUDING t
     }
     if (embed) {                                            // next step's input row (every thread knows t)
-        constexpr int NT = CPT > 0 ? FAST_NT : 1024;
         int64_t tt = t < 0 ? 0 : (t >= V ? V - 1 : t);
         const uint4* src = reinterpret_cast<const uint4*>(embed + (size_t)tt * H);
         uint4* dst = reinterpret_cast<uint4*>(h_out + (size_t)blockIdx.x * H);
@@ -396,15 +500,61 @@ __global__ __launch_bounds__(CPT > 0 ? FAST_NT : 1024) void pick_advance_batch_k
 }
 
 void launch_argmax_advance_batch(int dtype, const void* logits, int V, int ld, const SeqStateRef* tab, const SeqStateRef* single, int n, int64_t* ids_out,
-                                 const void* embed, void* h_out, int H, hipStream_t st) {
+                                 const void* embed, void* h_out, int H, hipStream_t st, bool rules) {
     LMX_REQUIRE((tab != nullptr) != (single != nullptr) && (tab || n == 1), "pick: give a device table or one by-value state");
+    LMX_REQUIRE(!rules || V <= RULES_MAX_V, "pick: the vocabulary is too large for the logits-processor bitmaps");
     const SeqStateRef one = single ? *single : SeqStateRef{};
     dispatch_dtype(dtype, "argmax_advance_batch", [&](auto t) {
         using T = LMX_T(t);
-        const auto kern = sample_cpt(V) == 32 ? pick_advance_batch_kernel<T, 32> : pick_advance_batch_kernel<T, 0>;
-        hipLaunchKernelGGL(kern, dim3(n), dim3(sample_cpt(V) > 0 ? FAST_NT : 1024), 0, st, (const T*)logits, V, ld, tab, one,
+        const auto kern = rules ? pick_advance_batch_kernel<T, 0, true> : sample_cpt(V) == 32 ? pick_advance_batch_kernel<T, 32> : pick_advance_batch_kernel<T, 0>;
+        hipLaunchKernelGGL(kern, dim3(n), dim3(!rules && sample_cpt(V) > 0 ? FAST_NT : 1024), rules ? rule_bits_bytes(V) : 0, st, (const T*)logits, V, ld, tab, one,
                            ids_out, (const T*)embed, (T*)h_out, H);
     });
+    LMX_CHECK_HIP(hipGetLastError());
+}
+
+// The ruled pick without the advance (kernels.h: launch_pick_rules): the prefill's first pick and the tests' entry point
+template <typename T>
+__global__ __launch_bounds__(1024) void pick_rules_kernel(const T* __restrict__ logits, int V, LogitRules lr, const int64_t* __restrict__ log, int log_cap,
+                                                          const int* __restrict__ n_out_ptr, int n_out_val, SampleParams p, uint32_t u32_override, int use_override,
+                                                          int64_t* __restrict__ out_tok, float* __restrict__ processed, uint8_t* __restrict__ keep_out) {
+    __shared__ SampleShared sh;
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    constexpr int NT = 1024;
+    const int n_out = n_out_ptr ? *n_out_ptr : n_out_val;
+    const RuleView<true> rv = build_rule_bitmaps<NT>(lr, log, n_out < log_cap ? n_out : log_cap, n_out, V);
+    if (processed) for (int i = threadIdx.x; i < V; i += NT) processed[i] = adjust(rv, i, to_f32(logits[i]));
+    int64_t t;
+    if (p.temperature > 0.f) {
+        const uint32_t u = use_override ? u32_override : philox_u32(p.seed_lo, p.seed_hi, (uint32_t)n_out);
+        t = sample_any<T, 0, true>(logits, V, p.temperature, p.top_p, p.top_k, u, sh, keep_out, rv);
+    } else {
+        t = argmax_row<T, NT, true>(logits, V, bv, bi, rv);
+    }
+    if (threadIdx.x == 0) *out_tok = t;
+}
+
+void launch_pick_rules(int dtype, const void* logits, int V, const LogitRules& rules, const int64_t* log, int log_cap, const int* n_out_ptr, int n_out,
+                       const SampleParams& p, const uint32_t* u32_override, int64_t* out_tok, float* processed, uint8_t* keep_out, hipStream_t st) {
+    LMX_REQUIRE(V > 0 && V <= RULES_MAX_V, "pick_rules: the vocabulary is too large for the logits-processor bitmaps");
+    LMX_REQUIRE(p.temperature <= 0.f || p.top_p > 0.f, "pick_rules: top_p must be positive");
+    LMX_REQUIRE(rules.n_eos >= 0 && rules.n_eos <= RULES_MAX_EOS && rules.n_suppress >= 0 && rules.n_suppress <= RULES_MAX_SUPPRESS && rules.n_prompt >= 0,
+                "pick_rules: at most 4 end-of-sequence ids and 16 suppressed ids");
+    dispatch_dtype(dtype, "pick_rules", [&](auto t) {
+        using T = LMX_T(t);
+        hipLaunchKernelGGL(pick_rules_kernel<T>, dim3(1), dim3(1024), rule_bits_bytes(V), st, (const T*)logits, V, rules, log, log_cap, n_out_ptr, n_out, p,
+                           u32_override ? *u32_override : 0u, u32_override ? 1 : 0, out_tok, processed, keep_out);
+    });
+    LMX_CHECK_HIP(hipGetLastError());
+}
+
+// the rules travel by value (kernel argument), like the stop rule: no host buffer to keep alive, no host synchronisation in the setter
+__global__ void set_logit_rules_kernel(LogitRules* dst, LogitRules v) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *dst = v;
+}
+void launch_set_logit_rules(LogitRules* dst, const LogitRules& v, hipStream_t st) {
+    hipLaunchKernelGGL(set_logit_rules_kernel, dim3(1), dim3(64), 0, st, dst, v);
     LMX_CHECK_HIP(hipGetLastError());
 }
 

@@ -86,6 +86,7 @@ _SIGS = {
     "lmx_seq_set_sampling": (c_int32, [c_void_p, c_float, c_float, c_int32, ctypes.c_uint64]),
     "lmx_seq_set_stop": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "lmx_seq_stopped": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "lmx_seq_set_logit_rules": (c_int32, [c_void_p, c_float, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
     "lmx_seq_reset": (c_int32, [c_void_p]),
     "lmx_seq_length": (c_int32, [c_void_p]),
     "lmx_prefill": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
@@ -122,6 +123,8 @@ _SIGS = {
     "lmx_op_decode_attn_batch_tab_bytes": (c_size_t, [c_int32]),
     "lmx_op_decode_attn_ws_bytes": (c_size_t, [c_int32] * 4),
     "lmx_op_sample": (c_int32, [c_int32, c_void_p, c_int32, c_float, c_float, c_int32, ctypes.c_uint64, c_void_p, POINTER(ctypes.c_uint32), c_void_p, c_void_p, c_void_p]),
+    "lmx_op_pick_rules": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                    c_float, c_float, c_int32, ctypes.c_uint64, POINTER(ctypes.c_uint32), c_void_p, c_void_p, c_void_p, c_void_p]),
     "lmx_op_argmax": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
     "lmx_op_ce_loss": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_void_p]),
     "lmx_op_rmsnorm_bwd": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),

@@ -157,7 +157,7 @@ class DecodeBatcher:
             raise m.error
 
     def submit_request(self, request: dict, make_emit: Callable[[int], Callable[[int], bool]], max_new_tokens: int) -> None:
-        """Hand a whole request (ids, images, mask, sampling, chunk) to the scheduler thread, which prefills it — together with the other requests waiting
+        """Hand a whole request (ids, images, mask, sampling, stop rule, logits-processor `rules`, chunk) to the scheduler thread, which prefills it — together with the other requests waiting
         at that moment, announced to the followers under tensor parallelism — between two decode steps and then steps it with the others.
         make_emit(budget) builds the request's on_token.  Blocks until the request finished."""
         m = _Member(None, None, 0)

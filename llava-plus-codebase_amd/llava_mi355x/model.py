@@ -937,16 +937,20 @@ class LlavaLlamaForCausalLM:
     @torch.no_grad()
     def generate_batch(self, prompts, images=None, max_new_tokens: int = 20, eos_token_id=None, run_ahead: int = 16,
                        prefill_chunk: int = 0, capacity: Optional[int] = None, attention_masks=None, do_sample: bool = False,
-                       temperature: float = 1.0, top_p: Optional[float] = None, top_k: Optional[int] = None, packed_prefill: bool = True):
+                       temperature: float = 1.0, top_p: Optional[float] = None, top_k: Optional[int] = None, packed_prefill: bool = True, rules=None):
         """Offline batch generation (greedy, or sampled on the device): the requests are prefilled TOGETHER (own image, own prompt length — no padding: their
         rows form one packed block walked in pieces of prefill_chunk x requests rows, every linear a single GEMM per piece; lmx_prefill_batch), then
         all of them decode together, `run_ahead` chained steps per host round trip; finished requests leave the batch.  packed_prefill=False prefills
         request by request (lmx_prefill, `prefill_chunk` rows at a time).
         prompts: list of LongTensor [L_i] / [1, L_i] (with -200 markers); images: list of per-request tensors or None.
+        rules: the logits processors (_rules_spec's dict of generate()'s kwargs, or its result) of every request, or a list with one entry (or None) per request.
         Returns a list of LongTensor [L_i + new_i] (input ids echoed, like generate())."""
         from .batching import DecodeBatch
         self._ensure_final()
         n_req = len(prompts)
+        rules = list(rules) if isinstance(rules, list) else [rules] * n_req
+        if len(rules) != n_req:
+            raise ValueError("generate_batch: `rules` needs one entry per request")
         images = images if images is not None else [None] * n_req
         eos = eos_token_id if eos_token_id is not None else getattr(self.config, "eos_token_id", None)
         eos_set = set(eos if isinstance(eos, (list, tuple)) else ([eos] if eos is not None else []))
@@ -957,8 +961,12 @@ class LlavaLlamaForCausalLM:
             masks = attention_masks if attention_masks is not None else [None] * n_req
             # tensor parallel: the images of ALL requests through one tower pass split over the ranks (every rank runs this same plan)
             pre = self._preencode_requests(images) if self.tp_world > 1 else [None] * n_req
-            for ids, img, am, ov in zip(prompts, images, masks, pre):
+            for ids, img, am, ov, rl in zip(prompts, images, masks, pre, rules):
                 ids = ids if ids.dim() == 2 else ids[None]
+                if isinstance(rl, dict):
+                    rl = self._rules_spec(rl, eos_set, ids.shape[1])
+                if rl is not None and self.tp_world > 1:
+                    raise NotImplementedError("logits processors under tensor parallelism: the follower replay does not carry them")
                 am = None if am is None else (am if am.dim() == 2 else am[None])
                 self._tls.plan_mask = None
                 self._tls.feats_override = ov
@@ -973,6 +981,7 @@ class LlavaLlamaForCausalLM:
                 cache = LmxKVCache(self, 1)
                 caches.append(cache)
                 self._set_stop(cache.seqs[0], self._stop_spec(eos_set))     # a member that reached EOS stops advancing inside the batched steps
+                self._set_rules(cache.seqs[0], rl, ids)
                 if not greedy:
                     seed = self._draw_seed()
                     check(lib.lmx_seq_set_sampling(cache.seqs[0], float(temperature), float(top_p if top_p is not None else 1.0), int(top_k or 0), seed),
@@ -1032,6 +1041,12 @@ class LlavaLlamaForCausalLM:
         eos_set = set(eos if isinstance(eos, (list, tuple)) else ([eos] if eos is not None else []))
         pad = pad_token_id if pad_token_id is not None else (getattr(self.config, "pad_token_id", None) or 0)
         greedy = (not do_sample) or (temperature is not None and temperature <= 1e-5)
+        # repetition_penalty, no_repeat_ngram_size, min_new_tokens / min_length, suppress_tokens, bad_words_ids: applied by the device picks (csrc/sampling.hip)
+        rules = self._rules_spec(kwargs, eos_set, L)
+        if rules is not None and num_beams != 1:
+            raise NotImplementedError("logits processors with num_beams != 1: HF applies them to the beams' log-softmax scores, which the beam kernels do not do")
+        if rules is not None and self.tp_world > 1:
+            raise NotImplementedError("logits processors under tensor parallelism: the follower replay does not carry them")
         rows: List[List[int]] = []
         if num_beams != 1:
             # GenerationMixin.beam_search / beam_sample + BeamSearchScorer (llava_mi355x/beam.py); transformers refuses a streamer here as well
@@ -1063,13 +1078,13 @@ class LlavaLlamaForCausalLM:
             outs = self.generate_batch([ids[b] for b in range(B)], row_images, max_new_tokens=max_new_tokens, eos_token_id=list(eos_set) or -1,
                                        run_ahead=run_ahead, prefill_chunk=prefill_chunk,
                                        attention_masks=None if attention_mask is None else [attention_mask[b] for b in range(B)],
-                                       do_sample=not greedy, temperature=temperature, top_p=top_p, top_k=top_k)
+                                       do_sample=not greedy, temperature=temperature, top_p=top_p, top_k=top_k, rules=rules)
             rows = [o[L:].tolist() for o in outs]
         else:
             for b in range(B):
                 row_mask = None if attention_mask is None else attention_mask[b:b + 1]
                 rows.append(self._generate_one(ids[b:b + 1], row_images[b], row_mask, greedy, temperature, top_p, top_k, max_new_tokens,
-                                               eos_set, streamer, stopping_criteria, run_ahead, prefill_chunk))
+                                               eos_set, streamer, stopping_criteria, run_ahead, prefill_chunk, rules))
         if streamer is not None:
             streamer.end()
         if self.tp_world > 1 and getattr(self, "p2p_active", False):
@@ -1140,7 +1155,56 @@ class LlavaLlamaForCausalLM:
         ln = (ctypes.c_int32 * max(1, len(kws)))(*[len(k) for k in kws])
         check(lib.lmx_seq_set_stop(seq, e, len(eos), f, ln, len(kws), stream_handle()), "lmx_seq_set_stop")
 
-    def _prepare_request(self, ids, images, attention_mask, sampling, stop=None, feats=None) -> dict:
+    @staticmethod
+    def _rules_spec(kw: Mapping, eos_set, prompt_len: int):
+        """generate()'s logits-processor arguments in the form lmx_seq_set_logit_rules takes them: (repetition_penalty, no_repeat_ngram_size, min_new_tokens,
+        eos ids, suppressed ids), or None when every one of them is neutral.  Validated the way HF's processors validate them; `min_length` folds into
+        min_new_tokens, the single-id entries of `bad_words_ids` into the suppressed ids."""
+        if isinstance(kw, tuple):
+            return kw
+        pen = kw.get("repetition_penalty")
+        pen = 1.0 if pen is None else pen
+        if isinstance(pen, bool) or not isinstance(pen, (int, float)) or not pen > 0:
+            raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {pen}")
+
+        def nonneg(name):
+            v = kw.get(name)
+            v = 0 if v is None else v
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"`{name}` has to be a non-negative integer, but is {v}")
+            return v
+        ngram, min_new, min_len = nonneg("no_repeat_ngram_size"), nonneg("min_new_tokens"), nonneg("min_length")
+        min_new = max(min_new, min_len - int(prompt_len))
+        sup = [int(t) for t in (kw.get("suppress_tokens") or [])]
+        for w in (kw.get("bad_words_ids") or []):
+            w = [int(t) for t in w]
+            if len(w) != 1:
+                raise NotImplementedError("bad_words_ids: only single-id entries are applied on the device")
+            sup.append(w[0])
+        sup = sorted(set(sup))
+        eos = sorted(int(e) for e in eos_set if e is not None and int(e) >= 0) if min_new > 0 else []
+        if not eos:
+            min_new = 0
+        if len(sup) > 16:
+            raise NotImplementedError("suppress_tokens + bad_words_ids: the device holds at most 16 suppressed ids")
+        if len(eos) > 4:
+            raise NotImplementedError("min_new_tokens: the device holds at most 4 end-of-sequence ids")
+        if float(pen) == 1.0 and ngram == 0 and min_new == 0 and not sup:
+            return None
+        return (float(pen), int(ngram), int(min_new), eos, sup)
+
+    def _set_rules(self, seq, rules, ids) -> None:
+        """Before the prefill, like the stop rule: token 1 follows the rules too.  `ids`: the row's input_ids as passed in (markers and padding included)."""
+        if not rules:
+            return
+        pen, ngram, min_new, eos, sup = rules
+        h = [int(v) for v in ids.reshape(-1).tolist()]
+        e = (ctypes.c_int64 * max(1, len(eos)))(*eos)
+        s = (ctypes.c_int64 * max(1, len(sup)))(*sup)
+        p = (ctypes.c_int64 * max(1, len(h)))(*h)
+        check(lib.lmx_seq_set_logit_rules(seq, pen, ngram, min_new, e, len(eos), s, len(sup), p, len(h), stream_handle()), "lmx_seq_set_logit_rules")
+
+    def _prepare_request(self, ids, images, attention_mask, sampling, stop=None, feats=None, rules=None) -> dict:
         """The RANK-LOCAL half of a request's prefill: image encode (the tower is replicated here; `feats` = the (features, hashes) pair of a batch-wide
         sharded pass, _preencode_requests, replaces it), splice, selection of the valid rows, a fresh sequence with its
         sampling state.  Nothing in here carries a decoder collective, so under tensor parallelism a failure (a bad request, an allocation) can still be
@@ -1186,6 +1250,7 @@ class LlavaLlamaForCausalLM:
                 check(lib.lmx_seq_set_sampling(cache.seqs[0], float(temperature), float(top_p if top_p is not None else 1.0), int(top_k or 0), int(seed)),
                       "lmx_seq_set_sampling")
             self._set_stop(cache.seqs[0], stop)          # before the prefill: its own pick (token 1) is tested too
+            self._set_rules(cache.seqs[0], rules, ids)
             return {"cache": cache, "embeds": embeds, "valid": valid}
         except BaseException:
             if cache is not None:
@@ -1238,11 +1303,11 @@ class LlavaLlamaForCausalLM:
         self._prefill_packed([p["cache"].seqs[0] for p in prepared], [self._packed_rows(p["embeds"], p["valid"]) for p in prepared], prefill_chunk)
         return None
 
-    def _prefill_request(self, ids, images, attention_mask, sampling, prefill_chunk: int = 0, return_logits: bool = False, stop=None):
+    def _prefill_request(self, ids, images, attention_mask, sampling, prefill_chunk: int = 0, return_logits: bool = False, stop=None, rules=None):
         """Image encode + splice + prefill of ONE request (ids [1, L]) into a fresh sequence; the first pick (argmax, or a draw when
         `sampling` = (temperature, top_p, top_k, seed) is given) is on the device when the stream gets there.  Shared by the request
         thread (generate) and the scheduler threads (batching.py, tp_serving.py)."""
-        p = self._prepare_request(ids, images, attention_mask, sampling, stop)
+        p = self._prepare_request(ids, images, attention_mask, sampling, stop, rules=rules)
         try:
             last = self._run_prepared([p], prefill_chunk, return_logits=return_logits)
             return (p["cache"], last) if return_logits else p["cache"]
@@ -1256,7 +1321,8 @@ class LlavaLlamaForCausalLM:
         prepared: List[dict] = []
         try:
             for r in reqs:
-                prepared.append(self._prepare_request(r["ids"].to(self.device), r["images"], r["attention_mask"], r["sampling"], r.get("stop")))
+                prepared.append(self._prepare_request(r["ids"].to(self.device), r["images"], r["attention_mask"], r["sampling"], r.get("stop"),
+                                                      rules=r.get("rules")))
             self._run_prepared(prepared, prefill_chunk)
             return [p["cache"] for p in prepared]
         except BaseException:
@@ -1265,7 +1331,7 @@ class LlavaLlamaForCausalLM:
             raise
 
     def _generate_one(self, ids, images, attention_mask, greedy, temperature, top_p, top_k, max_new_tokens, eos_set, streamer,
-                      stopping_criteria, run_ahead, prefill_chunk) -> List[int]:
+                      stopping_criteria, run_ahead, prefill_chunk, rules=None) -> List[int]:
         if max_new_tokens <= 0:
             return []
         crit = list(stopping_criteria) if stopping_criteria is not None else []
@@ -1295,11 +1361,11 @@ class LlavaLlamaForCausalLM:
             # prefilled TOGETHER, one GEMM per linear over all their rows (lmx_prefill_batch).  The request thread hands the request over and waits
             sampling = None if greedy else (float(temperature), top_p, top_k, int(torch.randint(0, 2 ** 62, (1,)).item()))
             request = {"ids": ids.cpu(), "images": images, "attention_mask": None if attention_mask is None else attention_mask.cpu(),
-                       "sampling": sampling, "prefill_chunk": int(prefill_chunk), "stop": stop, "out_ref": out}
+                       "sampling": sampling, "prefill_chunk": int(prefill_chunk), "stop": stop, "rules": rules, "out_ref": out}
             if getattr(batcher, "prepare_on_request_thread", False) and batcher.queued() < batcher.capacity:      # (a prepared request holds a sequence: bounded)
                 # the rank-local half of the prefill here, on this request's own thread and stream (beside the running decode steps and the other requests'
                 # prefills): image encode or feature-cache hit, splice, prefix-cache take.  The prefill thread then packs ready rows only
-                prepared = self._prepare_request(ids.to(self.device), images, attention_mask, sampling, stop)
+                prepared = self._prepare_request(ids.to(self.device), images, attention_mask, sampling, stop, rules=rules)
                 request["prepared"], request["rows"] = prepared, int(prepared["embeds"].shape[1])
                 # (from here the scheduler owns the prepared sequence: it closes it if the request never reaches a prefill)
             batcher.submit_request(request, make_emit, int(max_new_tokens))
@@ -1311,7 +1377,7 @@ class LlavaLlamaForCausalLM:
             gate.acquire()
         try:
             sampling = None if greedy else (float(temperature), top_p, top_k, self._draw_seed())
-            cache = self._prefill_request(ids, images, attention_mask, sampling, prefill_chunk, stop=stop)
+            cache = self._prefill_request(ids, images, attention_mask, sampling, prefill_chunk, stop=stop, rules=rules)
             seq = cache.seqs[0]
             if gate is not None:
                 torch.cuda.current_stream(self.device).synchronize()      # the next request's prefill starts when this one is done
