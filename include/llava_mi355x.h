@@ -356,6 +356,19 @@ int lmx_op_transpose(int32_t dtype, const void* src, int32_t ld, int32_t rows, i
 int lmx_op_gemm_wgrad(int32_t dtype, const void* dy, int32_t lddy, const void* x, int32_t ldx, int32_t rows, int32_t out_features, int32_t in_features, void* out,
                       int32_t ldo, void* stream);
 int lmx_op_gemm_wgrad_supported(int32_t dtype, int32_t lddy, int32_t ldx, int32_t rows, int32_t out_features, int32_t in_features, int32_t ldo);
+/* lmx_op_lora_wgrad: the gradient of one LoRA factor (peft's lora_A / lora_B are nn.Linear modules: grad_weight = grad_output^T @ input under
+ *   llava/train/train.py:873-889), out = T(alpha * sum_{row < rows} big[row][f] * small[row][j]) with both operands in their forward layout: big [rows][ld_big]
+ *   (F columns read: dy for lora_B, the layer input for lora_A), small [rows][ld_small] (R columns read: x A^T or dy B, R = the rank padded to a multiple of 64).
+ *   transposed = 0 stores out[f][j] (lora_B, [F][ld_out]), 1 stores out[j][f] (lora_A, [R_out][ld_out]); only j < R_out <= R is stored.  The rows are split
+ *   into n_slices slices (0 = chosen by the launcher) whose fp32 partial sums live in `workspace` (lmx_op_lora_wgrad_workspace bytes for the same rows, F, R,
+ *   n_slices; 16-byte aligned) and are added in slice order: no atomics, the same inputs give the same bits.  16-bit dtypes; rows and F multiples of 64,
+ *   R in {64, 128, 192, 256}, ld_big / ld_small multiples of 8, big and small 16-byte aligned and below 4 GiB: lmx_op_lora_wgrad_supported returns 1 for such a
+ *   call, 0 otherwise (the caller then takes the transposes + lmx_op_gemm; an unsupported lmx_op_lora_wgrad call FAILS). */
+int lmx_op_lora_wgrad(int32_t dtype, const void* big, int32_t ld_big, const void* small, int32_t ld_small, int32_t rows, int32_t F, int32_t R, int32_t R_out,
+                      float alpha, int32_t transposed, int32_t n_slices, void* out, int32_t ld_out, void* workspace, size_t workspace_bytes, void* stream);
+int lmx_op_lora_wgrad_supported(int32_t dtype, int32_t ld_big, int32_t ld_small, int32_t rows, int32_t F, int32_t R, int32_t R_out, int32_t transposed,
+                                int32_t ld_out);
+size_t lmx_op_lora_wgrad_workspace(int32_t rows, int32_t F, int32_t R, int32_t n_slices);
 int lmx_op_attn_bwd(int32_t dtype, int32_t head_dim, const void* q, const void* k, const void* v, const void* d_out, void* dq, float* dk32_scratch,
                     float* dv32_scratch, void* dk, void* dv, int32_t T, int32_t heads, int32_t kv_heads, int32_t ldq, int32_t ldk, int32_t ldo, float scale,
                     void* stream);

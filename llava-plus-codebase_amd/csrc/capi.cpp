@@ -674,6 +674,20 @@ int lmx_op_gemm_wgrad(int32_t dtype, const void* dy, int32_t lddy, const void* x
 int lmx_op_gemm_wgrad_supported(int32_t dtype, int32_t lddy, int32_t ldx, int32_t rows, int32_t out_features, int32_t in_features, int32_t ldo) {
     return gemm_wgrad_direct_ok(dtype, out_features, in_features, rows, lddy, ldx, ldo) ? 1 : 0;
 }
+int lmx_op_lora_wgrad(int32_t dtype, const void* big, int32_t ld_big, const void* small, int32_t ld_small, int32_t rows, int32_t F, int32_t R, int32_t R_out,
+                      float alpha, int32_t transposed, int32_t n_slices, void* out, int32_t ld_out, void* workspace, size_t workspace_bytes, void* stream) {
+    LMX_API_BEGIN
+    launch_lora_wgrad(dtype, big, ld_big, small, ld_small, rows, F, R, R_out, alpha, transposed, n_slices, out, ld_out, workspace, workspace_bytes, S(stream));
+    LMX_API_END
+}
+int lmx_op_lora_wgrad_supported(int32_t dtype, int32_t ld_big, int32_t ld_small, int32_t rows, int32_t F, int32_t R, int32_t R_out, int32_t transposed,
+                                int32_t ld_out) {
+    return lora_wgrad_ok(dtype, ld_big, ld_small, rows, F, R, R_out, transposed, ld_out) ? 1 : 0;
+}
+size_t lmx_op_lora_wgrad_workspace(int32_t rows, int32_t F, int32_t R, int32_t n_slices) {
+    if (rows < 64 || F < 64 || R < 1) return 0;
+    return lora_wgrad_workspace_bytes(rows, F, R, n_slices);
+}
 int lmx_op_attn_bwd(int32_t dtype, int32_t head_dim, const void* q, const void* k, const void* v, const void* d_out, void* dq, float* dk32_scratch,
                     float* dv32_scratch, void* dk, void* dv, int32_t T, int32_t heads, int32_t kv_heads, int32_t ldq, int32_t ldk, int32_t ldo, float scale,
                     void* stream) {

@@ -356,6 +356,13 @@ void launch_transpose(int dtype, const void* src, int ld, int rows, int cols, vo
 // gemm8t.hip: out[M][N] = sum_r dy[r][m] * x[r][n] with both operands in their forward layout (no transposes); gemm_wgrad_direct_ok = the shapes it takes
 bool gemm_wgrad_direct_ok(int dtype, int M, int N, int rows, int lddy, int ldx, int ldo);
 void launch_gemm_wgrad(int dtype, const void* dy, int lddy, const void* x, int ldx, int rows, int M, int N, void* out, int ldo, hipStream_t st);
+// lora.hip: out = T(alpha * sum_r big[r][f] * small[r][j]) for a LoRA factor, [F][R_out] or transposed [R_out][F]; both operands in their forward layout, the
+// rows split into slices whose fp32 partials (workspace) are summed in slice order.  lora_wgrad_ok = the shapes it takes; n_slices 0 = automatic
+bool lora_wgrad_ok(int dtype, int ld_big, int ld_small, int rows, int F, int R, int R_out, int transposed, int ld_out);
+int lora_wgrad_slices(int rows, int F, int n_slices);
+size_t lora_wgrad_workspace_bytes(int rows, int F, int R, int n_slices);
+void launch_lora_wgrad(int dtype, const void* big, int ld_big, const void* small, int ld_small, int rows, int F, int R, int R_out, float alpha, int transposed,
+                       int n_slices, void* out, int ld_out, void* workspace, size_t workspace_bytes, hipStream_t st);
 // matrix-core form for 16-bit models (attn_bwd.hip; LMX_ATTN_BWD_MFMA=0 keeps the VALU kernels): launch_attn_bwd takes it when attn_bwd_mfma_wanted()
 bool attn_bwd_mfma_wanted(int dtype, int D);
 void launch_attn_bwd_mfma(int dtype, int D, const void* q, const void* k, const void* v, const void* dO, void* dq, void* dk, void* dv, int Tn, int heads,

@@ -134,6 +134,10 @@ _SIGS = {
     "lmx_op_transpose": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
     "lmx_op_gemm_wgrad": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
     "lmx_op_gemm_wgrad_supported": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "lmx_op_lora_wgrad": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p, c_int32,
+                                    c_void_p, c_size_t, c_void_p]),
+    "lmx_op_lora_wgrad_supported": (c_int32, [c_int32] * 9),
+    "lmx_op_lora_wgrad_workspace": (c_size_t, [c_int32] * 4),
     "lmx_op_elementwise": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "lmx_op_cast_f32": (c_int32, [c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     "lmx_op_col_sum": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),

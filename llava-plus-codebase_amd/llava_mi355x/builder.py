@@ -94,9 +94,9 @@ def merge_lora(W: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scaling: float
     if tuple(A.shape) != (r, in_f) or tuple(B.shape) != (out_f, r):
         raise ValueError(f"LoRA factors A {tuple(A.shape)} / B {tuple(B.shape)} do not fit the weight {tuple(W.shape)}")
     rp = (r + 15) // 16 * 16                                               # the fp32 GEMM walks K in steps of 16: zero columns add nothing
-    x = torch.zeros((out_f, rp), dtype=torch.float32)
-    x[:, :r] = B.float()
-    w = torch.zeros((in_f, rp), dtype=torch.float32)
+    x = torch.zeros((out_f, rp), dtype=torch.float32, device=B.device)     # operands are built where the factors already are (no host round trip for
+    x[:, :r] = B.float()                                                   # factors that live on the device: TrainStep.merged_state_dict)
+    w = torch.zeros((in_f, rp), dtype=torch.float32, device=A.device)
     w[:, :r] = (A.float() * scaling).t()
     return ops.gemm(x.to(device), w.to(device), residual=W.to(device=device, dtype=torch.float32).contiguous())
 

@@ -28,8 +28,10 @@ def _need_cuda_rows(*ts):
 
 
 def gemm(x, w, bias=None, residual=None, act=_C.ACT_NONE, variant=0, out=None):
-    """act(x @ w.T + bias) (+ residual).  x [M,K], w [N,K]; SiLU·mul expects w as the fused [32 gate|32 up] layout."""
-    _need_cuda(x, w, bias, residual)
+    """act(x @ w.T + bias) (+ residual).  x [M,K], w [N,K]; SiLU·mul expects w as the fused [32 gate|32 up] layout.  x, residual and out may be column windows
+    of wider buffers (contiguous rows, free row stride: the entry point takes the strides); out may be the residual's own buffer."""
+    _need_cuda(w, bias)
+    _need_cuda_rows(x, residual, out)
     M, K = x.shape
     N = w.shape[0]
     n_out = N // 2 if act == _C.ACT_SILU_MUL else N
@@ -400,6 +402,35 @@ def gemm_wgrad(dy, x, out):
     assert dy.shape[0] == x.shape[0] and tuple(out.shape) == (dy.shape[1], x.shape[1])
     check(lib.lmx_op_gemm_wgrad(torch_dtype_code(dy.dtype), ptr(dy), dy.stride(0), ptr(x), x.stride(0), dy.shape[0], dy.shape[1], x.shape[1], ptr(out), out.stride(0),
                                 stream_handle()), "gemm_wgrad")
+    return out
+
+
+def lora_wgrad_ok(big, small, out, r_out=None, transposed=False):
+    """True if lmx_op_lora_wgrad takes this call (16-bit, rows and big's columns multiples of 64, small 64 / 128 / 192 / 256 columns wide, aligned)."""
+    if big.dtype == torch.float32 or big.dtype != small.dtype or out.dtype != big.dtype or big.stride(1) != 1 or small.stride(1) != 1 or out.stride(1) != 1:
+        return False
+    if big.shape[0] != small.shape[0] or (big.data_ptr() | small.data_ptr()) & 15:
+        return False
+    r_out = small.shape[1] if r_out is None else r_out
+    return bool(lib.lmx_op_lora_wgrad_supported(torch_dtype_code(big.dtype), big.stride(0), small.stride(0), big.shape[0], big.shape[1], small.shape[1], r_out,
+                                                int(transposed), out.stride(0)))
+
+
+def lora_wgrad(big, small, out=None, alpha=1.0, r_out=None, transposed=False, n_slices=0):
+    """out = alpha * big[rows, F]^T @ small[rows, R][:, :r_out], stored [F, r_out] or, transposed, [r_out, F]; both operands in their forward layout
+    (csrc/lora.hip).  The gradient of a LoRA factor: (dy, u) -> dB, (x, du) transposed -> dA.  Fails loudly on shapes lora_wgrad_ok rejects."""
+    _need_cuda_rows(big, small, out)
+    rows, F = big.shape
+    R = small.shape[1]
+    r_out = R if r_out is None else r_out
+    shape = (r_out, F) if transposed else (F, r_out)
+    if out is None:
+        out = torch.empty(shape, dtype=big.dtype, device=big.device)
+    assert small.shape[0] == rows and tuple(out.shape) == shape and out.dtype == big.dtype == small.dtype
+    nbytes = int(lib.lmx_op_lora_wgrad_workspace(rows, F, R, n_slices))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=big.device)
+    check(lib.lmx_op_lora_wgrad(torch_dtype_code(big.dtype), ptr(big), big.stride(0), ptr(small), small.stride(0), rows, F, R, r_out, float(alpha), int(transposed),
+                                int(n_slices), ptr(out), out.stride(0), ptr(ws), nbytes, stream_handle()), "lora_wgrad")
     return out
 
 

@@ -26,7 +26,8 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import Dict, List, Mapping, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -40,6 +41,29 @@ def _round_up(n: int, m: int) -> int:
     return -(-n // m) * m
 
 
+LORA_PAD = 64                     # adapters are stored with the rank padded to this (the K quantum of the GEMMs, the rank widths of csrc/lora.hip)
+LORA_MODULES = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")   # module order
+
+
+@dataclass
+class LoraConfig:
+    """peft's LoraConfig as the reference fills it (llava/train/train.py:873-889): rank, alpha, the decoder linears that get an adapter.  The default targets are what
+    find_all_linear_names (train.py:174-187) yields for this model: every decoder linear, no lm_head, nothing multimodal.  Dropout is not implemented."""
+    r: int
+    alpha: float
+    target_modules: Tuple[str, ...] = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+    use_rslora: bool = False
+
+    @property
+    def scaling(self) -> float:
+        return float(self.alpha) / math.sqrt(self.r) if self.use_rslora else float(self.alpha) / self.r
+
+
+def lora_unpad(name: str, t: torch.Tensor, r: int) -> torch.Tensor:
+    """The stored (rank-padded) factor -> what peft holds: lora_A [Rp, in] -> [r, in], lora_B [out, Rp] -> [out, r]."""
+    return (t[:r] if name.endswith("lora_A.weight") else t[:, :r]).detach().clone()
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # ZeRO-2 bookkeeping + collectives (no kernels: runs on any device, covered by a gloo world_size-2 test on CPU)
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -48,10 +72,11 @@ class ZeroPartition:
 
     sizes: [(name, numel)] in the order gradients become final (backward order).  Every parameter starts at a multiple of `align`
     elements (16-byte rows for the GEMMs); a bucket closes at the first parameter boundary past `bucket_elems` and is padded so that it
-    splits evenly over `world` ranks."""
+    splits evenly over `world` ranks.  rate_of (name -> learning rate): a bucket also closes where the rate changes, so no bucket mixes two rates and
+    `bucket_rate[b]` is the rate of all of bucket b (None without rate_of)."""
 
     def __init__(self, sizes: Sequence[Tuple[str, int]], world: int = 1, rank: int = 0, bucket_elems: int = 1 << 24, align: int = 64,
-                 no_close_after: Sequence[str] = ()):
+                 no_close_after: Sequence[str] = (), rate_of: Optional[Callable[[str], float]] = None):
         assert world >= 1 and 0 <= rank < world
         self.world, self.rank, self.align = int(world), int(rank), int(align)
         self.offset: Dict[str, int] = {}
@@ -59,10 +84,19 @@ class ZeroPartition:
         self.bucket_of: Dict[str, int] = {}
         self.buckets: List[Tuple[int, int]] = []
         self.members: List[List[str]] = []
+        self.bucket_rate: List[Optional[float]] = []
         pos, start, names = 0, 0, []
         hold = set(no_close_after)
         quantum = self.world * self.align
+        rate = None
         for name, n in sizes:
+            nxt = None if rate_of is None else float(rate_of(name))
+            if names and nxt != rate:                           # a rate boundary: the open bucket ends here
+                assert names[-1] not in hold, f"learning rates change inside a fused operand at {name}"
+                pos = start + _round_up(pos - start, quantum)
+                self.buckets.append((start, pos)); self.members.append(names); self.bucket_rate.append(rate)
+                start, names = pos, []
+            rate = nxt
             self.offset[name], self.numel[name] = pos, int(n)
             self.bucket_of[name] = len(self.buckets)
             names.append(name)
@@ -71,11 +105,11 @@ class ZeroPartition:
             # row size for world = 3, 5, 6, 7) would separate tensors the step uses as ONE operand (q | k | v)
             if pos - start >= bucket_elems and name not in hold:
                 pos = start + _round_up(pos - start, quantum)
-                self.buckets.append((start, pos)); self.members.append(names)
+                self.buckets.append((start, pos)); self.members.append(names); self.bucket_rate.append(rate)
                 start, names = pos, []
         if names:
             pos = start + _round_up(pos - start, quantum)
-            self.buckets.append((start, pos)); self.members.append(names)
+            self.buckets.append((start, pos)); self.members.append(names); self.bucket_rate.append(rate)
         self.total = pos
         self.shard_offset = []                      # where bucket b's owned slice sits in this rank's shard buffers
         acc = 0
@@ -156,7 +190,12 @@ class TrainStep:
 
     def __init__(self, config, weights: Mapping[str, torch.Tensor], dtype=torch.bfloat16, device="cuda", lr=2e-5, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, max_grad_norm=1.0, group=None, bucket_elems: Optional[int] = None, checkpoint: bool = False, max_positions: int = 2048,
-                 keep_layers: int = 0, keep_budget_bytes: Optional[int] = None, direct_wgrad: bool = True, attn_streams: int = 4):
+                 keep_layers: int = 0, keep_budget_bytes: Optional[int] = None, direct_wgrad: bool = True, attn_streams: int = 4,
+                 lora: Optional[LoraConfig] = None, lr_for: Optional[Callable[[str], float]] = None, train_base: Sequence[str] = (), lora_seed: int = 0):
+        """lora: train rank-r adapters on the decoder linears instead of the base weights (see the LoRA section below); train_base: base tensors that stay
+        trainable next to the adapters and the projector (`lm_head.weight`, `model.norm.weight`, `model.embed_tokens.weight`); lora_seed: seed of the CPU generator
+        the A factors are drawn from.  lr_for: name -> learning rate (as in self.p); None: self.lr for everything.  With lr_for, self.lr acts as the schedule's
+        base: bucket b steps with lr_for(name) * self.lr / the lr given here."""
         from .model import _projector_kind, _rope_theta
         self.config, self.dtype, self.device = config, dtype, torch.device(device)
         self.lr, self.betas, self.eps, self.wd, self.max_grad_norm = float(lr), tuple(betas), float(eps), float(weight_decay), float(max_grad_norm)
@@ -209,26 +248,99 @@ class TrainStep:
             bucket_elems = self.H * self.H                       # DeepSpeed's "auto" reduce_bucket_size = hidden_size^2
         # q | k | v of a layer form one fused operand of the step: no bucket boundary (padding) between them, whatever the world size
         fused = [f"model.layers.{l}.self_attn.{p}_proj.weight" for l in range(self.L) for p in ("q", "k")]
-        self.part = ZeroPartition([(n, int(np.prod(self.shapes[n]))) for n in order], self.world, self.rank, bucket_elems, no_close_after=fused)
+        nq = (self.nh + 2 * self.nkv) * self.D
+        self.lora, self.lr_for, self.base_lr = lora, lr_for, float(lr)
+        self.lora_mods: Tuple[str, ...] = ()
+        self._sB: Optional[Dict[str, torch.Tensor]] = None       # LoRA: scaling * B per adapter, valid until the parameters change
+        self.base: Dict[str, torch.Tensor] = {}                  # LoRA: the frozen base tensors, outside the flat buffers
+        self.p: Dict[str, torch.Tensor] = {}
+        self.g: Dict[str, torch.Tensor] = {}
+        self.qkv_w, self.qkv_g = [], []
+        flat_order = order
+        if lora is not None:
+            # ---- LoRA: only the adapters, the projector and `train_base` are parameters of the optimiser; the base lives in plain device tensors ----------
+            assert lora.r >= 1 and float(lora.alpha) > 0
+            self.lora_mods = tuple(m for m in LORA_MODULES if m.split(".")[1] in set(lora.target_modules))
+            unknown = set(lora.target_modules) - {m.split(".")[1] for m in LORA_MODULES}
+            if unknown or not self.lora_mods:
+                raise ValueError(f"LoRA target modules {sorted(unknown) or list(lora.target_modules)}: only the decoder linears {[m.split('.')[1] for m in LORA_MODULES]} take adapters")
+            extra = set(train_base)
+            if extra - {"lm_head.weight", "model.norm.weight", "model.embed_tokens.weight"}:
+                raise ValueError("train_base: only lm_head.weight, model.norm.weight and model.embed_tokens.weight can train next to the adapters")
+            self.Rp = _round_up(lora.r, LORA_PAD)
+            in_out = {"self_attn.q_proj": (self.H, self.nh * self.D), "self_attn.k_proj": (self.H, self.nkv * self.D), "self_attn.v_proj": (self.H, self.nkv * self.D),
+                      "self_attn.o_proj": (self.nh * self.D, self.H), "mlp.gate_proj": (self.H, self.I), "mlp.up_proj": (self.H, self.I), "mlp.down_proj": (self.I, self.H)}
+            groups = (("mlp.down_proj",), ("mlp.gate_proj", "mlp.up_proj"), ("self_attn.o_proj",), ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"))
+            flat_order = [n for n in ("lm_head.weight", "model.norm.weight") if n in extra]
+            fused = []
+            self.lora_groups: Dict[Tuple[int, str], Tuple[str, ...]] = {}            # (layer, first module of a group that shares its input) -> the group's targets
+            for l in reversed(range(self.L)):
+                for grp in groups:
+                    ts = tuple(m for m in grp if m in self.lora_mods)
+                    if not ts:
+                        continue
+                    self.lora_groups[(l, grp[0])] = ts
+                    a_names = [f"model.layers.{l}.{m}.lora_A.weight" for m in ts]
+                    flat_order += a_names + [f"model.layers.{l}.{m}.lora_B.weight" for m in ts]
+                    fused += a_names[:-1]                                            # the A factors of a group are ONE stacked operand: no padding between them
+                    for m in ts:
+                        self.shapes[f"model.layers.{l}.{m}.lora_A.weight"] = (self.Rp, in_out[m][0])
+                        self.shapes[f"model.layers.{l}.{m}.lora_B.weight"] = (in_out[m][1], self.Rp)
+            for j in reversed(range(len(self.proj_names) // 2)):
+                flat_order += [self.proj_names[2 * j + 1], self.proj_names[2 * j]]
+            if "model.embed_tokens.weight" in extra:
+                flat_order.append("model.embed_tokens.weight")
+            for l in range(self.L):
+                pre = f"model.layers.{l}.self_attn."
+                qkv = torch.empty((nq, self.H), dtype=dtype, device=self.device)     # q | k | v stay one fused operand: allocated as one
+                at = 0
+                for pn in ("q_proj", "k_proj", "v_proj"):
+                    rows = self.shapes[pre + pn + ".weight"][0]
+                    self.base[pre + pn + ".weight"] = qkv[at:at + rows]; at += rows
+                self.qkv_w.append(qkv); self.qkv_g.append(None)
+            for n in order:
+                if n not in flat_order:
+                    if n not in self.base:
+                        self.base[n] = torch.empty(self.shapes[n], dtype=dtype, device=self.device)
+                    self.base[n].copy_(w[n].to(device=self.device, dtype=dtype))
+        rate_of = None if lr_for is None else (lambda n: float(lr_for(n)))
+        self.part = ZeroPartition([(n, int(np.prod(self.shapes[n]))) for n in flat_order], self.world, self.rank, bucket_elems, no_close_after=fused, rate_of=rate_of)
         P = self.part
         self.flat_p = torch.zeros(P.total, dtype=dtype, device=self.device)
         self.flat_g = torch.zeros(P.total, dtype=dtype, device=self.device)
-        self.p: Dict[str, torch.Tensor] = {}
-        self.g: Dict[str, torch.Tensor] = {}
-        for n in order:
+        for n in flat_order:
             o, k = P.offset[n], P.numel[n]
             self.p[n] = self.flat_p[o:o + k].view(self.shapes[n])
             self.g[n] = self.flat_g[o:o + k].view(self.shapes[n])
-            self.p[n].copy_(w[n].to(device=self.device, dtype=dtype))
-        # q | k | v rows are adjacent in the flat buffer: one fused [(nh + 2 nkv) D, H] operand without a copy
-        self.qkv_w, self.qkv_g = [], []
-        nq = (self.nh + 2 * self.nkv) * self.D
-        for l in range(self.L):
-            o = P.offset[f"model.layers.{l}.self_attn.q_proj.weight"]
-            assert P.offset[f"model.layers.{l}.self_attn.k_proj.weight"] == o + self.nh * self.D * self.H
-            assert P.offset[f"model.layers.{l}.self_attn.v_proj.weight"] == o + (self.nh + self.nkv) * self.D * self.H
-            self.qkv_w.append(self.flat_p[o:o + nq * self.H].view(nq, self.H))
-            self.qkv_g.append(self.flat_g[o:o + nq * self.H].view(nq, self.H))
+            if n in w:
+                self.p[n].copy_(w[n].to(device=self.device, dtype=dtype))
+        if lora is None:
+            # q | k | v rows are adjacent in the flat buffer: one fused [(nh + 2 nkv) D, H] operand without a copy
+            for l in range(self.L):
+                o = P.offset[f"model.layers.{l}.self_attn.q_proj.weight"]
+                assert P.offset[f"model.layers.{l}.self_attn.k_proj.weight"] == o + self.nh * self.D * self.H
+                assert P.offset[f"model.layers.{l}.self_attn.v_proj.weight"] == o + (self.nh + self.nkv) * self.D * self.H
+                self.qkv_w.append(self.flat_p[o:o + nq * self.H].view(nq, self.H))
+                self.qkv_g.append(self.flat_g[o:o + nq * self.H].view(nq, self.H))
+        else:
+            self.p.update(self.base)                             # self.p resolves every name: the forward reads base and trainable tensors the same way
+            # peft's initialisation (LoraLayer.reset_lora_parameters): A = kaiming_uniform_(a = sqrt(5)), i.e. U(-1 / sqrt(in), 1 / sqrt(in)), drawn on the CPU
+            # in module order; B = 0.  Rows of A / columns of B past r are zero and stay zero (their gradients are products with zero columns; weight decay is 0).
+            gen = torch.Generator().manual_seed(int(lora_seed))
+            self.lora_A_stack: Dict[Tuple[int, str], torch.Tensor] = {}
+            for l in range(self.L):
+                for m in self.lora_mods:
+                    a = self.p[f"model.layers.{l}.{m}.lora_A.weight"]
+                    draw = torch.empty((lora.r, a.shape[1]), dtype=torch.float32)
+                    bound = 1.0 / math.sqrt(a.shape[1])
+                    draw.uniform_(-bound, bound, generator=gen)
+                    a[:lora.r].copy_(draw.to(dtype))
+            for (l, first), ts in self.lora_groups.items():
+                o = P.offset[f"model.layers.{l}.{ts[0]}.lora_A.weight"]
+                k_in = self.shapes[f"model.layers.{l}.{ts[0]}.lora_A.weight"][1]
+                for i, m in enumerate(ts):
+                    assert P.offset[f"model.layers.{l}.{m}.lora_A.weight"] == o + i * self.Rp * k_in
+                self.lora_A_stack[(l, first)] = self.flat_p[o:o + len(ts) * self.Rp * k_in].view(len(ts) * self.Rp, k_in)
         # ---- optimiser state for the owned slices only (ZeRO-2) -----------------------------------------------------------------------
         n_own = P.shard_elems
         self.master = torch.empty(n_own, dtype=torch.float32, device=self.device)
@@ -276,6 +388,88 @@ class TrainStep:
             pad[:, :N].copy_(dy)
             dy = pad
         return ops.gemm(dy, wt, residual=residual)
+
+    # ---- LoRA pieces: y = x W^T + scaling (x A^T) B^T per target linear ---------------------------------------------------------------------------
+    def _lora_down(self, l: int, first: str, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """u = x A^T for every target of the group that shares the input x, as ONE GEMM on the stacked A factors; {module: its [rows, Rp] column window of u}."""
+        ts = self.lora_groups.get((l, first), ()) if self.lora is not None else ()
+        if not ts:
+            return {}
+        u = ops.gemm(x, self.lora_A_stack[(l, first)])
+        return {m: u[:, i * self.Rp:(i + 1) * self.Rp] for i, m in enumerate(ts)}
+
+    def _lora_sB(self, l: int, m: str) -> torch.Tensor:
+        """scaling * B, [out, Rp]: the operand of the up-projection and of du = dy (scaling B).  Built once per optimiser step for all adapters (one pass over the
+        flat parameter buffer's copy) and dropped when the parameters change.  Rounded to the model dtype: exact when the scaling is a power of two
+        (alpha = 2 r of the reference's scripts), one extra 16-bit rounding of B otherwise (peft rounds the product u B^T instead)."""
+        if self._sB is None:
+            flat = self.flat_p * self.lora.scaling               # B factors are views into the flat buffer: scale it whole, read the same offsets
+            P = self.part
+            self._sB = {n: flat[P.offset[n]:P.offset[n] + P.numel[n]].view(self.shapes[n]) for n in self.g if n.endswith("lora_B.weight")}
+        return self._sB[f"model.layers.{l}.{m}.lora_B.weight"]
+
+    def _lora_up(self, l: int, m: str, u: torch.Tensor, y: torch.Tensor) -> None:
+        """y += u (scaling B)^T in place: the existing GEMM with K = Rp and residual = out = y (a column window of q|k|v through its row stride).  Every GEMM
+        epilogue, the split-K reducers included, reads residual[m][n] in the thread that then stores out[m][n], so the two may be the same buffer."""
+        ops.gemm(u, self._lora_sB(l, m), residual=y, out=y)
+
+    def _lora_backward(self, l: int, m: str, dy: torch.Tensor, x: torch.Tensor, u: torch.Tensor, into: Optional[torch.Tensor]) -> torch.Tensor:
+        """Gradients of one adapter from dy [rows, out], the linear's input x [rows, in] and the stashed u = x A^T; returns `into` + du A ([rows, in]: the adapter's
+        share of dx).  du = dy (scaling B); dB = scaling dy^T u; dA = du^T x — the two factor gradients on csrc/lora.hip where it takes the shape."""
+        An, Bn = f"model.layers.{l}.{m}.lora_A.weight", f"model.layers.{l}.{m}.lora_B.weight"
+        du = self._dgrad(dy, self._lora_sB(l, m))
+        if ops.lora_wgrad_ok(dy, u, self.g[Bn]):
+            ops.lora_wgrad(dy, u, self.g[Bn], alpha=self.lora.scaling)
+        else:                                                # the fp32 verification step, odd shapes: the two-transpose path
+            self._wgrad(dy, u * self.lora.scaling, self.g[Bn])
+        if ops.lora_wgrad_ok(x, du, self.g[An], transposed=True):
+            ops.lora_wgrad(x, du, self.g[An], transposed=True)
+        else:
+            self._wgrad(du, x, self.g[An])
+        return self._dgrad(du, self.p[An], residual=into)
+
+    def lora_state_dict(self) -> Dict[str, torch.Tensor]:
+        """Un-padded adapter factors, A [r, in] and B [out, r], keyed `model.layers.N.<module>.lora_A.weight` / `.lora_B.weight`."""
+        assert self.lora is not None, "not a LoRA step"
+        r, out = self.lora.r, {}
+        for l in range(self.L):
+            for m in self.lora_mods:
+                base = f"model.layers.{l}.{m}."
+                for f in ("lora_A.weight", "lora_B.weight"):
+                    out[base + f] = lora_unpad(base + f, self.p[base + f], r)
+        return out
+
+    def load_lora_state_dict(self, state: Mapping[str, torch.Tensor]) -> None:
+        """Set adapter factors (un-padded, keys as lora_state_dict gives them) and re-seed the fp32 master copies from them."""
+        assert self.lora is not None, "not a LoRA step"
+        r = self.lora.r
+        for k, v in state.items():
+            t = self.p[k]
+            (t[:r] if k.endswith("lora_A.weight") else t[:, :r]).copy_(v.to(device=self.device, dtype=self.dtype))
+        self._sync_master()
+
+    def merged_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The model with every adapter merged, W + scaling B A, in fp32 on the device through builder.merge_lora (what loading the saved adapter gives)."""
+        assert self.lora is not None, "not a LoRA step"
+        from .builder import merge_lora
+        ad = self.lora_state_dict()
+        out = {}
+        for n, t in self.p.items():
+            if ".lora_" in n:
+                continue
+            mod = n[:-len(".weight")] if n.endswith(".weight") else n
+            if mod + ".lora_A.weight" in ad:
+                out[n] = merge_lora(t.detach(), ad[mod + ".lora_A.weight"], ad[mod + ".lora_B.weight"], self.lora.scaling, self.device)      # all operands already on the device
+            else:
+                out[n] = t.detach().float()
+        return out
+
+    def _sync_master(self) -> None:
+        P = self.part
+        self._sB = None
+        for b in range(len(P.buckets)):
+            o0, o1 = P.owned(b)
+            P.shard_view(self.master, b).copy_(self.flat_p[o0:o1].float())
 
     def _attn_streams(self, n_items: int):
         """Context manager for the per-sample attention launches of one layer: `with self._attn_streams(n) as on: with on(i) as lane: ...` runs item i on side stream
@@ -339,6 +533,8 @@ class TrainStep:
         """Bytes one decoder layer's stash holds beyond its input rows (what _layer_forward returns: h, q|k|v with q and k rotated, attn, x1, h2, gate, up, act)."""
         es = torch.empty((), dtype=self.dtype).element_size()
         per_row = 3 * self.H + (self.nh + 2 * self.nkv) * self.D + self.nh * self.D + 3 * self.I
+        if self.lora is not None:
+            per_row += len(self.lora_mods) * self.Rp                       # the stashed u = x A^T of every adapter
         return int(rows) * per_row * es
 
     def set_trainable(self, predicate) -> None:
@@ -391,6 +587,11 @@ class TrainStep:
         W, nh, nkv, D = self.p, self.nh, self.nkv, self.D
         h = ops.rmsnorm(x, W[p + "input_layernorm.weight"], self.rms_eps)
         qkv = ops.gemm(h, self.qkv_w[l])
+        us: Dict[str, torch.Tensor] = {}
+        us.update(self._lora_down(l, "self_attn.q_proj", h))
+        for m, c0, c1 in (("self_attn.q_proj", 0, nh * D), ("self_attn.k_proj", nh * D, (nh + nkv) * D), ("self_attn.v_proj", (nh + nkv) * D, (nh + 2 * nkv) * D)):
+            if m in us:
+                self._lora_up(l, m, us[m], qkv[:, c0:c1])
         attn = torch.empty((x.shape[0], nh * D), dtype=x.dtype, device=x.device)
         self._zero_rows_outside(attn, spans)                                          # padding rows feed o_proj: finite zeros, as before
         # the forward's log-sum-exp, kept for the backward (FlashAttention-2's statistics); allocated on the step's stream BEFORE the samples spread over the side streams
@@ -416,29 +617,49 @@ class TrainStep:
                     else:
                         ops.flash_attn(rows, kc, vt, Tn, Tn, 0, nh, nkv, D, True, q_stride=qkv.stride(0), out=attn[a:b], lse=lses[i])
         x1 = ops.gemm(attn, W[p + "self_attn.o_proj.weight"], residual=x)
+        us.update(self._lora_down(l, "self_attn.o_proj", attn))
+        if "self_attn.o_proj" in us:
+            self._lora_up(l, "self_attn.o_proj", us["self_attn.o_proj"], x1)
         h2 = ops.rmsnorm(x1, W[p + "post_attention_layernorm.weight"], self.rms_eps)
         gate = ops.gemm(h2, W[p + "mlp.gate_proj.weight"])
         up = ops.gemm(h2, W[p + "mlp.up_proj.weight"])
+        us.update(self._lora_down(l, "mlp.gate_proj", h2))
+        if "mlp.gate_proj" in us:
+            self._lora_up(l, "mlp.gate_proj", us["mlp.gate_proj"], gate)
+        if "mlp.up_proj" in us:
+            self._lora_up(l, "mlp.up_proj", us["mlp.up_proj"], up)
         act = ops.elementwise(ops.EW_SWIGLU, gate, up)
         x2 = ops.gemm(act, W[p + "mlp.down_proj.weight"], residual=x1)
-        return x2, dict(x=x, h=h, qkv=qkv, attn=attn, lse=lses, x1=x1, h2=h2, gate=gate, up=up, act=act)
+        us.update(self._lora_down(l, "mlp.down_proj", act))
+        if "mlp.down_proj" in us:
+            self._lora_up(l, "mlp.down_proj", us["mlp.down_proj"], x2)
+        return x2, dict(x=x, h=h, qkv=qkv, attn=attn, lse=lses, x1=x1, h2=h2, gate=gate, up=up, act=act, u=us)
 
     def _layer_backward(self, l: int, st: dict, d: torch.Tensor, spans: List[Tuple[int, int]]) -> torch.Tensor:
         p = f"model.layers.{l}."
         W, G, nh, nkv, D = self.p, self.g, self.nh, self.nkv, self.D
         dt = _C.torch_dtype_code(d.dtype)
         # MLP: x2 = x1 + down(silu(gate) * up)
-        d_act = self._dgrad(d, W[p + "mlp.down_proj.weight"])
-        self._wgrad(d, st["act"], G[p + "mlp.down_proj.weight"])
+        # With LoRA the base wgrads are skipped (the base is not a parameter) and every target linear adds its adapter's gradients and its share of dx (`side`).
+        lora = self.lora is not None
+        us = st.get("u", {})
+        side = lambda m, dy, x, into=None: self._lora_backward(l, m, dy, x, us[m], into) if m in us else into
+        d_act = self._dgrad(d, W[p + "mlp.down_proj.weight"], residual=side("mlp.down_proj", d, st["act"]))
+        if not lora:
+            self._wgrad(d, st["act"], G[p + "mlp.down_proj.weight"])
         dg, du = ops.swiglu_bwd(st["gate"], st["up"], d_act)
-        self._wgrad(dg, st["h2"], G[p + "mlp.gate_proj.weight"])
-        self._wgrad(du, st["h2"], G[p + "mlp.up_proj.weight"])
-        dh2 = self._dgrad(du, W[p + "mlp.up_proj.weight"], residual=self._dgrad(dg, W[p + "mlp.gate_proj.weight"]))
-        dx1, dw = ops.rmsnorm_bwd(st["x1"], W[p + "post_attention_layernorm.weight"], dh2, self.rms_eps, residual=d)     # d joins over the skip connection
-        ops.cast_f32(dw, G[p + "post_attention_layernorm.weight"])
+        if not lora:
+            self._wgrad(dg, st["h2"], G[p + "mlp.gate_proj.weight"])
+            self._wgrad(du, st["h2"], G[p + "mlp.up_proj.weight"])
+        s2 = side("mlp.up_proj", du, st["h2"], side("mlp.gate_proj", dg, st["h2"]))
+        dh2 = self._dgrad(du, W[p + "mlp.up_proj.weight"], residual=self._dgrad(dg, W[p + "mlp.gate_proj.weight"], residual=s2))
+        dx1, dw = ops.rmsnorm_bwd(st["x1"], W[p + "post_attention_layernorm.weight"], dh2, self.rms_eps, want_dw=not lora, residual=d)     # d joins over the skip connection
+        if not lora:
+            ops.cast_f32(dw, G[p + "post_attention_layernorm.weight"])
         # attention: x1 = x + o_proj(attn)
-        d_attn = self._dgrad(dx1, W[p + "self_attn.o_proj.weight"])
-        self._wgrad(dx1, st["attn"], G[p + "self_attn.o_proj.weight"])
+        d_attn = self._dgrad(dx1, W[p + "self_attn.o_proj.weight"], residual=side("self_attn.o_proj", dx1, st["attn"]))
+        if not lora:
+            self._wgrad(dx1, st["attn"], G[p + "self_attn.o_proj.weight"])
         qkv = st["qkv"]
         dqkv = torch.empty_like(qkv)
         self._zero_rows_outside(dqkv, spans)
@@ -464,7 +685,14 @@ class TrainStep:
                               "attn_bwd")
                     # un-rotate dq | dk in place: they are adjacent heads of the same rows
                     check(lib.lmx_op_rope_bwd(dt, _C.ptr(dq_rows), _C.ptr(dq_rows), _C.ptr(self.rope), 0, Tn, nh + nkv, D, ld, _C.stream_handle()), "rope_bwd")
-        dh = self._dgrad(dqkv, self.qkv_w[l])
+        s3 = None
+        for m, c0, c1 in (("self_attn.q_proj", 0, nh * D), ("self_attn.k_proj", nh * D, (nh + nkv) * D), ("self_attn.v_proj", (nh + nkv) * D, (nh + 2 * nkv) * D)):
+            s3 = side(m, dqkv[:, c0:c1], st["h"], s3)
+        dh = self._dgrad(dqkv, self.qkv_w[l], residual=s3)
+        if lora:
+            dx, _ = ops.rmsnorm_bwd(st["x"], W[p + "input_layernorm.weight"], dh, self.rms_eps, want_dw=False, residual=dx1)
+            self._mark_ready([f"{p}{m}.lora_{f}.weight" for m in self.lora_mods for f in ("A", "B")])
+            return dx
         self._wgrad(dqkv, st["h"], self.qkv_g[l])
         dx, dw = ops.rmsnorm_bwd(st["x"], W[p + "input_layernorm.weight"], dh, self.rms_eps, residual=dx1)
         ops.cast_f32(dw, G[p + "input_layernorm.weight"])
@@ -562,10 +790,12 @@ class TrainStep:
         self._ready.clear(); self._pending.clear()
         dlogits = dlogits[0]
         dhn = self._dgrad(dlogits, self.p["lm_head.weight"])
-        self._wgrad(dlogits, hn, self.g["lm_head.weight"])
-        d, dw = ops.rmsnorm_bwd(x, self.p["model.norm.weight"], dhn, self.rms_eps)
-        ops.cast_f32(dw, self.g["model.norm.weight"])
-        self._mark_ready(["lm_head.weight", "model.norm.weight"])
+        if "lm_head.weight" in self.g:                           # with LoRA the base is not a parameter: a base tensor has a gradient only if `train_base` names it
+            self._wgrad(dlogits, hn, self.g["lm_head.weight"])
+        d, dw = ops.rmsnorm_bwd(x, self.p["model.norm.weight"], dhn, self.rms_eps, want_dw="model.norm.weight" in self.g)
+        if "model.norm.weight" in self.g:
+            ops.cast_f32(dw, self.g["model.norm.weight"])
+        self._mark_ready([n for n in ("lm_head.weight", "model.norm.weight") if n in self.g])
         del logits, dlogits
         for l in reversed(range(self.L)):
             st = stash[l]
@@ -573,7 +803,8 @@ class TrainStep:
                 _, st = self._layer_forward(l, st["x"], spans)
             d = self._layer_backward(l, st, d, spans)
             stash[l] = None
-        dE = torch.zeros((self.V, self.H), dtype=torch.float32, device=dev)
+        want_dE = "model.embed_tokens.weight" in self.g
+        dE = torch.zeros((self.V, self.H), dtype=torch.float32, device=dev) if want_dE else None       # LoRA: no [V, H] fp32 table
         dfeats = torch.zeros_like(feats) if (feats is not None and pst is not None) else None
         ops.embed_bwd(src_d, d, dE, dfeats)
         if pst is not None:
@@ -582,8 +813,9 @@ class TrainStep:
             for n in self.proj_names:          # a text-only micro-batch: the projector took no part
                 self.g[n].zero_()
             self._mark_ready(self.proj_names)
-        ops.cast_f32(dE.view(-1), self.g["model.embed_tokens.weight"].view(-1))
-        self._mark_ready(["model.embed_tokens.weight"])
+        if want_dE:
+            ops.cast_f32(dE.view(-1), self.g["model.embed_tokens.weight"].view(-1))
+            self._mark_ready(["model.embed_tokens.weight"])
         return loss, count
 
     # ---- optimiser ------------------------------------------------------------------------------------------------------------------------
@@ -603,10 +835,13 @@ class TrainStep:
         P.all_reduce_scalar(self.gnorm_sq, self.group)
         for b in range(len(P.buckets)):
             view = lambda t: P.shard_view(t, b)
-            ops.adamw(view(self.p_shard), view(self.g_shard), view(self.master), view(self.exp_avg), view(self.exp_avg_sq), self.lr, self.betas, self.eps,
+            # lr_for: every bucket holds one rate (ZeroPartition closes buckets at rate boundaries); self.lr / base_lr is the schedule's factor
+            lr = self.lr if P.bucket_rate[b] is None else P.bucket_rate[b] * (self.lr / self.base_lr if self.base_lr != 0.0 else 0.0)
+            ops.adamw(view(self.p_shard), view(self.g_shard), view(self.master), view(self.exp_avg), view(self.exp_avg_sq), lr, self.betas, self.eps,
                       self.wd, self.step_count, gnorm_sq=self.gnorm_sq if self.max_grad_norm > 0 else None, max_grad_norm=self.max_grad_norm)
             P.all_gather(self.flat_p, self.p_shard, b, self.group)
         self.last_grad_norm = None
+        self._sB = None                                          # the parameters moved
 
     def grad_norm(self) -> float:
         """Global gradient norm of the last step (host read: a sync)."""
@@ -617,5 +852,10 @@ class TrainStep:
         self.optimizer_step()
         return loss, count
 
+    def trainable_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The tensors the optimiser owns (with LoRA: the padded adapter factors, the projector and `train_base`; without: everything)."""
+        return {n: self.p[n].detach().clone() for n in self.g}
+
     def state_dict(self) -> Dict[str, torch.Tensor]:
+        """Every tensor the forward reads, by name (with LoRA: the base as it is, un-merged, and the padded adapter factors)."""
         return {n: t.detach().clone() for n, t in self.p.items()}

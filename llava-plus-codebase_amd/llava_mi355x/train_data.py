@@ -59,7 +59,9 @@ class DataArguments:
 @dataclass
 class TrainingArguments:
     """The fields of the reference's TrainingArguments (a transformers.TrainingArguments subclass, train.py:83-111) that this package's training entry reads;
-    the HF Trainer / DeepSpeed / bitsandbytes / LoRA knobs have no counterpart here (out of scope)."""
+    the HF Trainer / DeepSpeed / bitsandbytes knobs have no counterpart here (out of scope).  The lora_* fields are the reference's (train.py:110-115,
+    same defaults); the training entry takes lora_dropout 0.0, lora_bias "none" and bits 16 only and refuses the rest.  lora_weight_path is carried for the scripts'
+    command lines only: the reference declares it and never reads it, and neither does this entry."""
     output_dir: str = "./checkpoints"
     model_max_length: int = field(default=512, metadata={"help": "Maximum sequence length. Sequences will be right padded (and possibly truncated)."})
     per_device_train_batch_size: int = 16
@@ -78,6 +80,13 @@ class TrainingArguments:
     fp16: bool = False
     gradient_checkpointing: bool = False
     freeze_mm_mlp_adapter: bool = False
+    bits: int = 16
+    lora_enable: bool = False
+    lora_r: int = 64
+    lora_alpha: int = 16
+    lora_dropout: float = 0.05
+    lora_weight_path: str = ""
+    lora_bias: str = "none"
     mm_projector_lr: Optional[float] = None
     group_by_modality_length: bool = False
     seed: int = 42

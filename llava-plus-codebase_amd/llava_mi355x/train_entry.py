@@ -8,12 +8,16 @@ the HF Trainer, around llava_mi355x/train.py: TrainStep instead.
                                                                        rows from the adapter file, which of the two matrices trains
     lr_at                          HF get_scheduler("cosine" | "linear" | "constant", warm-up = ceil(ratio x steps)) — the scripts' --lr_scheduler_type / --warmup_ratio
     save_checkpoint                llava/train/train.py:185-214        projector-only `mm_projector.bin` when tune_mm_mlp_adapter, else the whole state dict
+    save_lora_adapter              llava/train/train.py:987-997        --lora_enable: peft's adapter_config.json + adapter_model.safetensors, non_lora_trainables.bin,
+                                                                       config.json — the directory builder.load_pretrained_model(path, base, "...lora...") loads
     train                          llava/train/train.py:805-1000       template by --version, pad = unk, vision setup, dataset + collator (train_data.py), step loop
 
 Here a model is a (config, HF-named weight dict) pair — TrainStep owns the parameters in its flat ZeRO-2 buffers, the CLIP tower is the frozen inference tower of
 llava_mi355x/model.py (clip_encoder.py:25: `requires_grad_(False)`), its output enters the step as data.  Freezing (tune_mm_mlp_adapter, freeze_backbone,
-freeze_mm_mlp_adapter) = the frozen tensors' gradients never reach the optimiser (TrainStep.set_trainable).  Out of scope, as SURVEY §2 has it: DeepSpeed / HF
-Trainer plumbing, bitsandbytes, LoRA, MPT, checkpoint resumption."""
+freeze_mm_mlp_adapter) = the frozen tensors' gradients never reach the optimiser (TrainStep.set_trainable).  LoRA (--lora_enable, train.py:873-889) =
+TrainStep(lora=LoraConfig): the base leaves the optimiser's buffers altogether, rank-r adapters on every decoder linear and the projector train, and
+mm_projector_lr gives the projector its own rate (llava_trainer.py:150-237).  Out of scope, as SURVEY §2 has it: DeepSpeed / HF Trainer plumbing, bitsandbytes
+(bits < 16), LoRA dropout and trained LoRA biases, MPT, checkpoint resumption."""
 from __future__ import annotations
 
 import json
@@ -172,12 +176,42 @@ def save_checkpoint(output_dir: str, config, state: Mapping[str, torch.Tensor], 
     return path
 
 
+NON_LORA_PREFIX = "base_model.model."          # PeftModel -> LoraModel -> LlavaLlamaForCausalLM: the prefix peft puts before every key of the wrapped model
+
+
+def save_lora_adapter(output_dir: str, config, *, r: int, lora_alpha: float, target_modules, use_rslora: bool, lora_state: Mapping[str, torch.Tensor],
+                      non_lora_state: Mapping[str, torch.Tensor]) -> str:
+    """What the reference leaves in output_dir after a LoRA run (llava/train/train.py:987-997: model.config.save_pretrained, model.save_pretrained ->
+    peft, torch.save(non_lora_state_dict)):
+        adapter_config.json           peft's LoraConfig fields that the loader reads
+        adapter_model.safetensors     `base_model.model.model.layers.N.self_attn.q_proj.lora_A.weight` [r, in] / `.lora_B.weight` [out, r] (un-padded)
+        non_lora_trainables.bin       the other trained tensors (the projector, ...) as `base_model.model.model.mm_projector.*`
+        config.json
+    lora_state: TrainStep.lora_state_dict(); non_lora_state: HF-named tensors (`mm_projector.*` or `model.mm_projector.*`).  Returns the adapter file's path."""
+    from safetensors.torch import save_file
+    os.makedirs(output_dir, exist_ok=True)
+    with open(os.path.join(output_dir, "adapter_config.json"), "w") as f:
+        json.dump({"peft_type": "LORA", "task_type": "CAUSAL_LM", "r": int(r), "lora_alpha": lora_alpha, "lora_dropout": 0.0, "bias": "none",
+                   "target_modules": sorted(target_modules), "use_rslora": bool(use_rslora), "fan_in_fan_out": False, "modules_to_save": None,
+                   "inference_mode": True, "base_model_name_or_path": getattr(config, "_name_or_path", None)}, f, indent=2)
+    path = os.path.join(output_dir, "adapter_model.safetensors")
+    save_file({NON_LORA_PREFIX + k: v.detach().cpu().contiguous() for k, v in lora_state.items()}, path)
+    named = {NON_LORA_PREFIX + (("model." + k) if k.startswith("mm_projector.") else k): v.detach().cpu() for k, v in non_lora_state.items()}
+    torch.save(named, os.path.join(output_dir, "non_lora_trainables.bin"))
+    if hasattr(config, "to_json_string"):
+        with open(os.path.join(output_dir, "config.json"), "w") as f:
+            f.write(config.to_json_string())
+    return path
+
+
 def train(model_args, data_args, training_args, *, config, weights: MutableMapping[str, torch.Tensor], tokenizer, vision_tower: Optional[Callable] = None,
           group=None, device="cuda", log: Optional[Callable[[dict], None]] = None) -> Dict[str, object]:
     """The reference's train() with the loaded pieces passed in: `config` + `weights` = the language model (HF names; builder.iter_checkpoint reads a
     checkpoint into such a dict), `tokenizer`, `vision_tower` = the frozen tower of the inference model (LlavaLlamaForCausalLM.get_vision_tower(): callable
     on pixel batches, with .image_processor and .hidden_size).  One process per GPU; `group` = the data-parallel group (ZeRO-2 inside TrainStep; every rank
-    walks its own stride of the shuffled sample order).  Returns {"losses", "steps", "checkpoint", "state"}."""
+    walks its own stride of the shuffled sample order).  Returns {"losses", "steps", "checkpoint", "state", "frozen", "train_step"}: "state" = the step's state
+    dict (with lora_enable: the trained tensors only), "train_step" = the live TrainStep, for callers that go on with it (merged_state_dict(), further steps) — it
+    owns every device buffer of the run, so drop the reference to free them."""
     from .train import TrainStep
     from .train_data import make_supervised_data_module
     dtype = torch.float16 if training_args.fp16 else (torch.bfloat16 if training_args.bf16 else torch.float32)
@@ -221,8 +255,23 @@ def train(model_args, data_args, training_args, *, config, weights: MutableMappi
                 frozen.add(key)
     elif model_args.freeze_backbone:
         frozen |= {k for k in weights if k.startswith("model.")}
+    # ---- LoRA (train.py:873-889) and the projector's own rate (llava_trainer.py:150-237) ----------------------------------------------------------------------
+    lora = None
+    if getattr(training_args, "lora_enable", False):
+        if float(training_args.lora_dropout) != 0.0:
+            raise NotImplementedError(f"lora_dropout must be 0.0 here (got {training_args.lora_dropout}): LoRA dropout is not implemented")
+        if training_args.lora_bias != "none":
+            raise NotImplementedError(f"lora_bias must be 'none' (got {training_args.lora_bias!r}): trained LoRA biases are not implemented")
+        if int(getattr(training_args, "bits", 16)) != 16:
+            raise NotImplementedError(f"bits must be 16 (got {training_args.bits}): quantised LoRA is not implemented")
+        if model_args.tune_mm_mlp_adapter or model_args.freeze_backbone:
+            raise NotImplementedError("lora_enable with tune_mm_mlp_adapter / freeze_backbone is not wired")
+        from .train import LoraConfig
+        lora = LoraConfig(r=int(training_args.lora_r), alpha=training_args.lora_alpha)
+    lr_for = None
     if training_args.mm_projector_lr is not None:
-        raise NotImplementedError("mm_projector_lr (a second learning rate for the projector) is not wired")
+        proj_lr, base_lr = float(training_args.mm_projector_lr), float(training_args.learning_rate)
+        lr_for = lambda name: proj_lr if "mm_projector" in name else base_lr
     # ---- data (train.py:963-964) ------------------------------------------------------------------------------------------------------------------------------
     module = make_supervised_data_module(tokenizer=tokenizer, data_args=data_args)
     dataset, collate = module["train_dataset"], module["data_collator"]
@@ -239,7 +288,8 @@ def train(model_args, data_args, training_args, *, config, weights: MutableMappi
     ts = TrainStep(config, {k: v for k, v in weights.items() if "vision_tower" not in k and not k.startswith("vision.")}, dtype=dtype, device=device,
                    lr=training_args.learning_rate, betas=(training_args.adam_beta1, training_args.adam_beta2), eps=training_args.adam_epsilon,
                    weight_decay=training_args.weight_decay, max_grad_norm=training_args.max_grad_norm, group=group,
-                   checkpoint=bool(training_args.gradient_checkpointing), max_positions=max(2048, int(tokenizer.model_max_length) + 1024))
+                   checkpoint=bool(training_args.gradient_checkpointing), max_positions=max(2048, int(tokenizer.model_max_length) + 1024), lora=lora, lr_for=lr_for,
+                   lora_seed=int(training_args.seed))
     ts.set_trainable(lambda name: (("model." + name) if name.startswith("mm_projector.") else name) not in frozen)
     gen = torch.Generator().manual_seed(int(training_args.seed))
     sampler = None
@@ -271,9 +321,17 @@ def train(model_args, data_args, training_args, *, config, weights: MutableMappi
                 losses.append(rec["loss"])
                 if log is not None:
                     log(rec)
-    state = ts.state_dict()
-    path = save_checkpoint(training_args.output_dir, config, state, model_args) if rank == 0 and training_args.output_dir else None
+    # LoRA: only what trained is read back (the adapters, padded, and the projector); the frozen base, 13.5 GB for 7B, is not cloned
+    state = ts.trainable_state_dict() if lora is not None else ts.state_dict()
+    if lora is not None:
+        path = None
+        if rank == 0 and training_args.output_dir:
+            non_lora = {k: v for k, v in state.items() if k in ts.g and ".lora_" not in k and (("model." + k) if k.startswith("mm_projector.") else k) not in frozen}
+            path = save_lora_adapter(training_args.output_dir, config, r=lora.r, lora_alpha=lora.alpha, target_modules=lora.target_modules, use_rslora=lora.use_rslora,
+                                     lora_state=ts.lora_state_dict(), non_lora_state=non_lora)
+    else:
+        path = save_checkpoint(training_args.output_dir, config, state, model_args) if rank == 0 and training_args.output_dir else None
     if rank == 0 and training_args.output_dir:
         with open(os.path.join(training_args.output_dir, "trainer_state.json"), "w") as f:
             json.dump({"global_step": step, "log_history": [{"step": (i + 1) * max(1, int(training_args.logging_steps or 1)), "loss": l} for i, l in enumerate(losses)]}, f)   # a record every logging_steps steps
-    return {"losses": losses, "steps": step, "checkpoint": path, "state": state, "frozen": sorted(frozen)}
+    return {"losses": losses, "steps": step, "checkpoint": path, "state": state, "frozen": sorted(frozen), "train_step": ts}
