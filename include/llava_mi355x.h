@@ -369,6 +369,29 @@ int lmx_op_lora_wgrad(int32_t dtype, const void* big, int32_t ld_big, const void
 int lmx_op_lora_wgrad_supported(int32_t dtype, int32_t ld_big, int32_t ld_small, int32_t rows, int32_t F, int32_t R, int32_t R_out, int32_t transposed,
                                 int32_t ld_out);
 size_t lmx_op_lora_wgrad_workspace(int32_t rows, int32_t F, int32_t R, int32_t n_slices);
+/* LoRA dropout (peft: lora_B(lora_A(dropout(x))), p = 0.05 in the reference's LoRA scripts: llava/train/train.py:113, :879).  The mask is a pure function:
+ *   Philox4x32-10, one call per aligned group of 8 columns, counter = (row, col >> 3, stream_id, step), key = seed (lo, hi); the four output words are eight
+ *   16-bit lanes, column c takes word (c & 7) >> 1 (low half for even c) and is kept iff lane >= round(p * 65536); kept values are T(x * fp32(1 / (1 - p))), one
+ *   rounding, dropped ones +0.  `row` counts from the operand's first row, columns from its first column.  0 <= p < 1.
+ * lmx_dropout_keep_host: the keep mask on the host, keep[rows][cols] bytes of 0 / 1 (no GPU involved).
+ * lmx_op_dropout: out = dropout(x), fp32 / bf16 / f16, cols and the row strides multiples of 8, 16-byte aligned (lmx_op_dropout_supported); out may be x.
+ * lmx_op_dropout_add: into = T(into + mask * scale * t), the sum in fp32 (the adapter's share of dx, t = du A).
+ * lmx_op_lora_down_dropout: u[:, g Rp .. (g + 1) Rp) = dropout_g(x) A_g^T for the G <= 3 adapters that share x (A = their stacked factors [G Rp][lda], adapter g
+ *   masks with stream_id = stream0 + g); the mask is applied in registers, no masked copy of x is written.  16-bit dtypes, rows and K multiples of 64, Rp in
+ *   {64, 128, 192, 256}, strides multiples of 8, 16-byte aligned: lmx_op_lora_down_dropout_supported returns 1 for such a call (an unsupported call FAILS).
+ * lmx_op_lora_wgrad_dropout: lmx_op_lora_wgrad with the mask applied to `big` (dA = du^T dropout(x), transposed = 1); same shapes, workspace and determinism. */
+int lmx_dropout_keep_host(double p, uint64_t seed, uint32_t step, uint32_t stream_id, int32_t rows, int32_t cols, uint8_t* keep);
+int lmx_op_dropout(int32_t dtype, const void* x, int32_t ldx, void* out, int32_t ldo, int32_t rows, int32_t cols, double p, uint64_t seed, uint32_t step,
+                   uint32_t stream_id, void* stream);
+int lmx_op_dropout_add(int32_t dtype, void* into, int32_t ld_into, const void* t, int32_t ldt, int32_t rows, int32_t cols, double p, uint64_t seed, uint32_t step,
+                       uint32_t stream_id, void* stream);
+int lmx_op_dropout_supported(int32_t dtype, int32_t ldx, int32_t ldo, int32_t rows, int32_t cols);
+int lmx_op_lora_down_dropout(int32_t dtype, const void* x, int32_t ldx, const void* A, int32_t lda, void* u, int32_t ldu, int32_t rows, int32_t K, int32_t Rp, int32_t G,
+                             double p, uint64_t seed, uint32_t step, uint32_t stream0, void* stream);
+int lmx_op_lora_down_dropout_supported(int32_t dtype, int32_t ldx, int32_t lda, int32_t ldu, int32_t rows, int32_t K, int32_t Rp, int32_t G);
+int lmx_op_lora_wgrad_dropout(int32_t dtype, const void* big, int32_t ld_big, const void* small, int32_t ld_small, int32_t rows, int32_t F, int32_t R, int32_t R_out,
+                              float alpha, int32_t transposed, int32_t n_slices, void* out, int32_t ld_out, void* workspace, size_t workspace_bytes, double p,
+                              uint64_t seed, uint32_t step, uint32_t stream_id, void* stream);
 int lmx_op_attn_bwd(int32_t dtype, int32_t head_dim, const void* q, const void* k, const void* v, const void* d_out, void* dq, float* dk32_scratch,
                     float* dv32_scratch, void* dk, void* dv, int32_t T, int32_t heads, int32_t kv_heads, int32_t ldq, int32_t ldk, int32_t ldo, float scale,
                     void* stream);

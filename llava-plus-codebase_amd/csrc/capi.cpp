@@ -688,6 +688,49 @@ size_t lmx_op_lora_wgrad_workspace(int32_t rows, int32_t F, int32_t R, int32_t n
     if (rows < 64 || F < 64 || R < 1) return 0;
     return lora_wgrad_workspace_bytes(rows, F, R, n_slices);
 }
+int lmx_op_lora_wgrad_dropout(int32_t dtype, const void* big, int32_t ld_big, const void* small, int32_t ld_small, int32_t rows, int32_t F, int32_t R, int32_t R_out,
+                              float alpha, int32_t transposed, int32_t n_slices, void* out, int32_t ld_out, void* workspace, size_t workspace_bytes, double p,
+                              uint64_t seed, uint32_t step, uint32_t stream_id, void* stream) {
+    LMX_API_BEGIN
+    launch_lora_wgrad_dropout(dtype, big, ld_big, small, ld_small, rows, F, R, R_out, alpha, transposed, n_slices, out, ld_out, workspace, workspace_bytes, p, seed,
+                              step, stream_id, S(stream));
+    LMX_API_END
+}
+int lmx_op_lora_down_dropout(int32_t dtype, const void* x, int32_t ldx, const void* A, int32_t lda, void* u, int32_t ldu, int32_t rows, int32_t K, int32_t Rp, int32_t G,
+                             double p, uint64_t seed, uint32_t step, uint32_t stream0, void* stream) {
+    LMX_API_BEGIN
+    launch_lora_down_dropout(dtype, x, ldx, A, lda, u, ldu, rows, K, Rp, G, p, seed, step, stream0, S(stream));
+    LMX_API_END
+}
+int lmx_op_lora_down_dropout_supported(int32_t dtype, int32_t ldx, int32_t lda, int32_t ldu, int32_t rows, int32_t K, int32_t Rp, int32_t G) {
+    return lora_down_dropout_ok(dtype, ldx, lda, ldu, rows, K, Rp, G) ? 1 : 0;
+}
+int lmx_op_dropout(int32_t dtype, const void* x, int32_t ldx, void* out, int32_t ldo, int32_t rows, int32_t cols, double p, uint64_t seed, uint32_t step,
+                   uint32_t stream_id, void* stream) {
+    LMX_API_BEGIN
+    launch_dropout(dtype, x, ldx, out, ldo, rows, cols, p, seed, step, stream_id, 0, S(stream));
+    LMX_API_END
+}
+int lmx_op_dropout_add(int32_t dtype, void* into, int32_t ld_into, const void* t, int32_t ldt, int32_t rows, int32_t cols, double p, uint64_t seed, uint32_t step,
+                       uint32_t stream_id, void* stream) {
+    LMX_API_BEGIN
+    launch_dropout(dtype, t, ldt, into, ld_into, rows, cols, p, seed, step, stream_id, 1, S(stream));
+    LMX_API_END
+}
+int lmx_op_dropout_supported(int32_t dtype, int32_t ldx, int32_t ldo, int32_t rows, int32_t cols) { return dropout_ok(dtype, ldx, ldo, rows, cols) ? 1 : 0; }
+int lmx_dropout_keep_host(double p, uint64_t seed, uint32_t step, uint32_t stream_id, int32_t rows, int32_t cols, uint8_t* keep) {
+    LMX_API_BEGIN
+    LMX_REQUIRE(p >= 0.0 && p < 1.0, "dropout_keep_host: p must be in [0, 1)");
+    LMX_REQUIRE(rows >= 0 && cols >= 0, "dropout_keep_host: rows and cols must not be negative");
+    LMX_REQUIRE(keep || (int64_t)rows * cols == 0, "dropout_keep_host: null output");
+    const DropSpec d = make_drop_spec(p, seed, step, stream_id);
+    for (int32_t r = 0; r < rows; ++r)
+        for (int32_t c8 = 0; c8 * 8 < cols; ++c8) {
+            const uint32_t m = dropout_keep8(d, (uint32_t)r, (uint32_t)c8);
+            for (int32_t j = 0; j < 8 && c8 * 8 + j < cols; ++j) keep[(size_t)r * cols + c8 * 8 + j] = (uint8_t)(m >> j & 1);
+        }
+    LMX_API_END
+}
 int lmx_op_attn_bwd(int32_t dtype, int32_t head_dim, const void* q, const void* k, const void* v, const void* d_out, void* dq, float* dk32_scratch,
                     float* dv32_scratch, void* dk, void* dv, int32_t T, int32_t heads, int32_t kv_heads, int32_t ldq, int32_t ldk, int32_t ldo, float scale,
                     void* stream) {

@@ -598,4 +598,50 @@ void launch_cast(int sd, int dd, const void* src, void* dst, size_t n, hipStream
     LMX_CHECK_HIP(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// LoRA dropout, materialising forms (dropout.h holds the mask).  One thread per 8-column group = one Philox call.
+//   dropout_kernel       out = kept ? T(x * scale) : +0                       (peft: lora_dropout(x); out may be x)
+//   dropout_add_kernel   into = T(into + (kept ? t * scale : 0)) in fp32      (the adapter's share of dx: the mask on t = du A)
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T, bool ADD>
+__global__ __launch_bounds__(256) void dropout_kernel(const T* x, int ldx, T* out, int ldo, int rows, int c8n, DropSpec d) {
+#pragma clang fp contract(off)
+    const size_t n = (size_t)rows * c8n;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const uint32_t row = (uint32_t)(i / c8n), c8 = (uint32_t)(i - (size_t)row * c8n);
+        const uint32_t keep = dropout_keep8(d, row, c8);
+        float v[8], o[8];
+        load8<T>(x + (size_t)row * ldx + c8 * 8, v);
+        T* op = out + (size_t)row * ldo + c8 * 8;
+        if constexpr (ADD) load8<T>(op, o);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float s = v[e] * d.scale;
+            if constexpr (ADD) o[e] = (keep >> e & 1) ? o[e] + s : o[e];
+            else o[e] = (keep >> e & 1) ? s : 0.f;
+        }
+        store8<T>(op, o);
+    }
+}
+
+bool dropout_ok(int dtype, int ldx, int ldo, int rows, int cols) {
+    return (dtype == kBF16 || dtype == kF16 || dtype == kF32) && rows > 0 && cols > 0 && cols % 8 == 0 && ldx >= cols && ldo >= cols && ldx % 8 == 0 && ldo % 8 == 0;
+}
+
+void launch_dropout(int dtype, const void* x, int ldx, void* out, int ldo, int rows, int cols, double p, uint64_t seed, uint32_t step, uint32_t stream, int add,
+                    hipStream_t st) {
+    dispatch_dtype(dtype, add ? "dropout_add" : "dropout", [&](auto t) {
+        using T = LMX_T(t);
+        LMX_REQUIRE(dropout_ok(dtype, ldx, ldo, rows, cols), "dropout: columns and row strides must be multiples of 8");
+        LMX_REQUIRE(p >= 0.0 && p < 1.0, "dropout: p must be in [0, 1)");
+        LMX_REQUIRE(x && out && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0, "dropout: operands must be 16-byte aligned");
+        const DropSpec d = make_drop_spec(p, seed, step, stream);
+        const int64_t n = (int64_t)rows * (cols / 8);
+        const int grid = (int)(cdiv64(n, 256) < 8192 ? cdiv64(n, 256) : 8192);
+        if (add) hipLaunchKernelGGL((dropout_kernel<T, true>), dim3(grid), dim3(256), 0, st, (const T*)x, ldx, (T*)out, ldo, rows, cols / 8, d);
+        else hipLaunchKernelGGL((dropout_kernel<T, false>), dim3(grid), dim3(256), 0, st, (const T*)x, ldx, (T*)out, ldo, rows, cols / 8, d);
+    });
+    LMX_CHECK_HIP(hipGetLastError());
+}
+
 }  // namespace lmx

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include "dropout.h"
 
 namespace lmx {
 
@@ -363,6 +364,19 @@ int lora_wgrad_slices(int rows, int F, int n_slices);
 size_t lora_wgrad_workspace_bytes(int rows, int F, int R, int n_slices);
 void launch_lora_wgrad(int dtype, const void* big, int ld_big, const void* small, int ld_small, int rows, int F, int R, int R_out, float alpha, int transposed,
                        int n_slices, void* out, int ld_out, void* workspace, size_t workspace_bytes, hipStream_t st);
+// the same product with the LoRA dropout mask (dropout.h) applied to `big` in registers, rows counted from the operand's first row: dA = du^T dropout(x)
+void launch_lora_wgrad_dropout(int dtype, const void* big, int ld_big, const void* small, int ld_small, int rows, int F, int R, int R_out, float alpha,
+                               int transposed, int n_slices, void* out, int ld_out, void* workspace, size_t workspace_bytes, double p, uint64_t seed, uint32_t step,
+                               uint32_t stream, hipStream_t st);
+// lora.hip: u[:, g Rp .. (g + 1) Rp) = dropout_g(x) A_g^T for the G <= 3 adapters that share the input x (A [G Rp][K], adapter g on stream stream0 + g); the mask is
+// applied to x's chunks in registers, no masked copy of x leaves the chip.  lora_down_dropout_ok = the shapes it takes
+bool lora_down_dropout_ok(int dtype, int ldx, int lda, int ldu, int rows, int K, int Rp, int G);
+void launch_lora_down_dropout(int dtype, const void* x, int ldx, const void* A, int lda, void* u, int ldu, int rows, int K, int Rp, int G, double p, uint64_t seed,
+                              uint32_t step, uint32_t stream0, hipStream_t st);
+// elementwise.hip: the materialising forms.  add = 0: out = dropout(x) (out may be x); add = 1: out = T(out + mask * scale * x) in fp32
+bool dropout_ok(int dtype, int ldx, int ldo, int rows, int cols);
+void launch_dropout(int dtype, const void* x, int ldx, void* out, int ldo, int rows, int cols, double p, uint64_t seed, uint32_t step, uint32_t stream, int add,
+                    hipStream_t st);
 // matrix-core form for 16-bit models (attn_bwd.hip; LMX_ATTN_BWD_MFMA=0 keeps the VALU kernels): launch_attn_bwd takes it when attn_bwd_mfma_wanted()
 bool attn_bwd_mfma_wanted(int dtype, int D);
 void launch_attn_bwd_mfma(int dtype, int D, const void* q, const void* k, const void* v, const void* dO, void* dq, void* dk, void* dv, int Tn, int heads,

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint8, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libllava_mi355x.so")
@@ -138,6 +138,15 @@ _SIGS = {
                                     c_void_p, c_size_t, c_void_p]),
     "lmx_op_lora_wgrad_supported": (c_int32, [c_int32] * 9),
     "lmx_op_lora_wgrad_workspace": (c_size_t, [c_int32] * 4),
+    "lmx_op_lora_wgrad_dropout": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p,
+                                            c_int32, c_void_p, c_size_t, c_double, c_uint64, c_uint32, c_uint32, c_void_p]),
+    "lmx_op_lora_down_dropout": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, c_uint64,
+                                           c_uint32, c_uint32, c_void_p]),
+    "lmx_op_lora_down_dropout_supported": (c_int32, [c_int32] * 8),
+    "lmx_op_dropout": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_double, c_uint64, c_uint32, c_uint32, c_void_p]),
+    "lmx_op_dropout_add": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_double, c_uint64, c_uint32, c_uint32, c_void_p]),
+    "lmx_op_dropout_supported": (c_int32, [c_int32] * 5),
+    "lmx_dropout_keep_host": (c_int32, [c_double, c_uint64, c_uint32, c_uint32, c_int32, c_int32, c_void_p]),
     "lmx_op_elementwise": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "lmx_op_cast_f32": (c_int32, [c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     "lmx_op_col_sum": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),

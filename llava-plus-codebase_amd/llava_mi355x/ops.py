@@ -434,6 +434,91 @@ def lora_wgrad(big, small, out=None, alpha=1.0, r_out=None, transposed=False, n_
     return out
 
 
+def _drop_args(p, seed, step, stream):
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability must be in [0, 1) (got {p})")
+    return p, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, int(stream) & 0xFFFFFFFF
+
+
+def dropout_ok(x, out=None):
+    """True if lmx_op_dropout / lmx_op_dropout_add take these operands (2-D, contiguous rows, columns and row strides multiples of 8, 16-byte aligned)."""
+    out = x if out is None else out
+    if x.dim() != 2 or out.dim() != 2 or x.stride(1) != 1 or out.stride(1) != 1 or x.dtype != out.dtype or x.shape != out.shape or (x.data_ptr() | out.data_ptr()) & 15:
+        return False
+    if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return False
+    return bool(lib.lmx_op_dropout_supported(torch_dtype_code(x.dtype), x.stride(0), out.stride(0), x.shape[0], x.shape[1]))
+
+
+def dropout(x, p, seed, step, stream, out=None):
+    """The LoRA dropout of x [rows, cols] (csrc/dropout.h, dropout.py): kept elements T(x * fp32(1 / (1 - p))), dropped ones +0, the mask a function of
+    (seed, row, column, stream, step).  The materialising form: the fp32 verification step, shapes the fused kernels refuse, and their yardstick.  out may be x."""
+    _need_cuda_rows(x, out)
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    assert out.shape == x.shape and out.dtype == x.dtype
+    p, seed, step, stream = _drop_args(p, seed, step, stream)
+    check(lib.lmx_op_dropout(torch_dtype_code(x.dtype), ptr(x), x.stride(0), ptr(out), out.stride(0), x.shape[0], x.shape[1], p, seed, step, stream, stream_handle()),
+          "dropout")
+    return out
+
+
+def dropout_add(into, t, p, seed, step, stream):
+    """into <- T(into + mask * scale * t), the sum in fp32: the adapter's share of dx, with the mask of the adapter's input on t = du A."""
+    _need_cuda_rows(into, t)
+    assert into.shape == t.shape and into.dtype == t.dtype
+    p, seed, step, stream = _drop_args(p, seed, step, stream)
+    check(lib.lmx_op_dropout_add(torch_dtype_code(t.dtype), ptr(into), into.stride(0), ptr(t), t.stride(0), t.shape[0], t.shape[1], p, seed, step, stream,
+                                 stream_handle()), "dropout_add")
+    return into
+
+
+def lora_down_dropout_ok(x, A_stack, G, out=None):
+    """True if lmx_op_lora_down_dropout takes this call (16-bit, rows and K multiples of 64, Rp = A_stack rows / G in {64, 128, 192, 256}, G <= 3, aligned)."""
+    if x.dim() != 2 or A_stack.dim() != 2 or x.dtype == torch.float32 or x.dtype != A_stack.dtype or x.stride(1) != 1 or A_stack.stride(1) != 1:
+        return False
+    if G < 1 or A_stack.shape[0] % G or A_stack.shape[1] != x.shape[1] or (x.data_ptr() | A_stack.data_ptr()) & 15:
+        return False
+    if out is not None and (out.dtype != x.dtype or out.stride(1) != 1 or tuple(out.shape) != (x.shape[0], A_stack.shape[0]) or out.data_ptr() & 15):
+        return False
+    ldu = A_stack.shape[0] if out is None else out.stride(0)
+    return bool(lib.lmx_op_lora_down_dropout_supported(torch_dtype_code(x.dtype), x.stride(0), A_stack.stride(0), ldu, x.shape[0], x.shape[1], A_stack.shape[0] // G, G))
+
+
+def lora_down_dropout(x, A_stack, G, p, seed, step, stream0, out=None):
+    """u [rows, G Rp] with u[:, g Rp:(g + 1) Rp] = dropout_g(x) @ A_g^T for the G adapters that share the input x (A_stack [G Rp, K]; adapter g masks with stream
+    stream0 + g).  The mask is applied inside the kernel (csrc/lora.hip): no masked copy of x is written.  Fails loudly on shapes lora_down_dropout_ok rejects."""
+    _need_cuda_rows(x, A_stack, out)
+    rows, K = x.shape
+    if out is None:
+        out = torch.empty((rows, A_stack.shape[0]), dtype=x.dtype, device=x.device)
+    assert A_stack.shape[0] % G == 0 and A_stack.shape[1] == K and tuple(out.shape) == (rows, A_stack.shape[0]) and out.dtype == x.dtype == A_stack.dtype
+    p, seed, step, stream0 = _drop_args(p, seed, step, stream0)
+    check(lib.lmx_op_lora_down_dropout(torch_dtype_code(x.dtype), ptr(x), x.stride(0), ptr(A_stack), A_stack.stride(0), ptr(out), out.stride(0), rows, K,
+                                       A_stack.shape[0] // G, int(G), p, seed, step, stream0, stream_handle()), "lora_down_dropout")
+    return out
+
+
+def lora_wgrad_dropout(big, small, p, seed, step, stream, out=None, alpha=1.0, r_out=None, transposed=False, n_slices=0):
+    """lora_wgrad with the LoRA dropout mask applied to `big` inside the kernel: dA = du^T dropout(x) for (x, du), transposed.  Takes what lora_wgrad_ok takes."""
+    _need_cuda_rows(big, small, out)
+    rows, F = big.shape
+    R = small.shape[1]
+    r_out = R if r_out is None else r_out
+    shape = (r_out, F) if transposed else (F, r_out)
+    if out is None:
+        out = torch.empty(shape, dtype=big.dtype, device=big.device)
+    assert small.shape[0] == rows and tuple(out.shape) == shape and out.dtype == big.dtype == small.dtype
+    p, seed, step, stream = _drop_args(p, seed, step, stream)
+    nbytes = int(lib.lmx_op_lora_wgrad_workspace(rows, F, R, n_slices))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=big.device)
+    check(lib.lmx_op_lora_wgrad_dropout(torch_dtype_code(big.dtype), ptr(big), big.stride(0), ptr(small), small.stride(0), rows, F, R, r_out, float(alpha),
+                                        int(transposed), int(n_slices), ptr(out), out.stride(0), ptr(ws), nbytes, p, seed, step, stream, stream_handle()),
+          "lora_wgrad_dropout")
+    return out
+
+
 def transpose_padded(x, multiple):
     """x [r, c] -> [c, roundup(r, multiple)] with zero columns past r: the operand layout of a GEMM that contracts over r."""
     _need_cuda_rows(x)

@@ -48,11 +48,18 @@ LORA_MODULES = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "sel
 @dataclass
 class LoraConfig:
     """peft's LoraConfig as the reference fills it (llava/train/train.py:873-889): rank, alpha, the decoder linears that get an adapter.  The default targets are what
-    find_all_linear_names (train.py:174-187) yields for this model: every decoder linear, no lm_head, nothing multimodal.  Dropout is not implemented."""
+    find_all_linear_names (train.py:174-187) yields for this model: every decoder linear, no lm_head, nothing multimodal.  dropout: peft's lora_dropout, the
+    probability with which an element of an adapter's input is zeroed (the reference's scripts run 0.05, train.py:113); 0 <= dropout < 1, realised as
+    round(dropout * 65536) / 65536 by the counter-based mask of dropout.py."""
     r: int
     alpha: float
     target_modules: Tuple[str, ...] = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
     use_rslora: bool = False
+    dropout: float = 0.0
+
+    def __post_init__(self):
+        if not 0.0 <= float(self.dropout) < 1.0:
+            raise ValueError(f"LoraConfig.dropout must be in [0, 1) (got {self.dropout})")
 
     @property
     def scaling(self) -> float:
@@ -191,11 +198,13 @@ class TrainStep:
     def __init__(self, config, weights: Mapping[str, torch.Tensor], dtype=torch.bfloat16, device="cuda", lr=2e-5, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, max_grad_norm=1.0, group=None, bucket_elems: Optional[int] = None, checkpoint: bool = False, max_positions: int = 2048,
                  keep_layers: int = 0, keep_budget_bytes: Optional[int] = None, direct_wgrad: bool = True, attn_streams: int = 4,
-                 lora: Optional[LoraConfig] = None, lr_for: Optional[Callable[[str], float]] = None, train_base: Sequence[str] = (), lora_seed: int = 0):
+                 lora: Optional[LoraConfig] = None, lr_for: Optional[Callable[[str], float]] = None, train_base: Sequence[str] = (), lora_seed: int = 0,
+                 dropout_seed: Optional[int] = None):
         """lora: train rank-r adapters on the decoder linears instead of the base weights (see the LoRA section below); train_base: base tensors that stay
         trainable next to the adapters and the projector (`lm_head.weight`, `model.norm.weight`, `model.embed_tokens.weight`); lora_seed: seed of the CPU generator
         the A factors are drawn from.  lr_for: name -> learning rate (as in self.p); None: self.lr for everything.  With lr_for, self.lr acts as the schedule's
-        base: bucket b steps with lr_for(name) * self.lr / the lr given here."""
+        base: bucket b steps with lr_for(name) * self.lr / the lr given here.  dropout_seed: the 64-bit key of the LoRA dropout masks (default: lora_seed);
+        self.dropout_step counts the forward_backward calls that drew masks (every training call) and is the masks' step counter (settable: the same seed and step give the same masks)."""
         from .model import _projector_kind, _rope_theta
         self.config, self.dtype, self.device = config, dtype, torch.device(device)
         self.lr, self.betas, self.eps, self.wd, self.max_grad_norm = float(lr), tuple(betas), float(eps), float(weight_decay), float(max_grad_norm)
@@ -250,6 +259,10 @@ class TrainStep:
         fused = [f"model.layers.{l}.self_attn.{p}_proj.weight" for l in range(self.L) for p in ("q", "k")]
         nq = (self.nh + 2 * self.nkv) * self.D
         self.lora, self.lr_for, self.base_lr = lora, lr_for, float(lr)
+        self.dropout_seed = int(lora_seed if dropout_seed is None else dropout_seed)
+        self.dropout_step = 0                                    # advanced by every forward_backward call that draws masks (a micro-batch), not by the optimiser
+        self._drop_on = True                                     # False inside a forward_backward(dropout=False) call: the adapters see x itself
+        self._drop_step = 0                                      # the step of the call that is running: recomputed layers and the backward read the same one
         self.lora_mods: Tuple[str, ...] = ()
         self._sB: Optional[Dict[str, torch.Tensor]] = None       # LoRA: scaling * B per adapter, valid until the parameters change
         self.base: Dict[str, torch.Tensor] = {}                  # LoRA: the frozen base tensors, outside the flat buffers
@@ -395,8 +408,44 @@ class TrainStep:
         ts = self.lora_groups.get((l, first), ()) if self.lora is not None else ()
         if not ts:
             return {}
-        u = ops.gemm(x, self.lora_A_stack[(l, first)])
+        A = self.lora_A_stack[(l, first)]
+        if self._drop_on and self.lora.dropout > 0.0:
+            # u = dropout_m(x) A_m^T, every adapter under its own mask.  The mask is applied inside csrc/lora.hip's down kernel; where that kernel does not take
+            # the call (the fp32 verification step, odd shapes) the masked input is materialised per adapter (ops.dropout) for the plain GEMM.
+            Rp, drop = self.Rp, self._drop()
+            u = torch.empty((x.shape[0], len(ts) * Rp), dtype=x.dtype, device=x.device)
+            sid = [self._drop_stream(l, m) for m in ts]
+            if sid == list(range(sid[0], sid[0] + len(ts))) and ops.lora_down_dropout_ok(x, A, len(ts), out=u):
+                ops.lora_down_dropout(x, A, len(ts), *drop, sid[0], out=u)
+            else:
+                for i in range(len(ts)):
+                    A_i, u_i = A[i * Rp:(i + 1) * Rp], u[:, i * Rp:(i + 1) * Rp]
+                    if ops.lora_down_dropout_ok(x, A_i, 1, out=u_i):
+                        ops.lora_down_dropout(x, A_i, 1, *drop, sid[i], out=u_i)
+                    else:
+                        ops.gemm(ops.dropout(x, *drop, sid[i]), A_i, out=u_i)
+        else:
+            u = ops.gemm(x, A)
         return {m: u[:, i * self.Rp:(i + 1) * self.Rp] for i, m in enumerate(ts)}
+
+    def _drop_stream(self, l: int, m: str) -> int:
+        """The mask stream of one adapter: rank << 16 | layer << 3 | index of the module in LORA_MODULES."""
+        from .dropout import stream_id
+        return stream_id(self.rank, l, LORA_MODULES.index(m))
+
+    def _drop(self) -> Tuple[float, int, int]:
+        return float(self.lora.dropout), self.dropout_seed, self._drop_step
+
+    def lora_keep_mask(self, layer: int, module: str, rows: int, cols: int, step: Optional[int] = None) -> np.ndarray:
+        """bool [rows, cols]: which elements of the input of adapter `module` (`q_proj` or `self_attn.q_proj`) of `layer` are kept; rows are the packed rows of this
+        rank's block in the order forward_backward packs them (sample after sample, valid positions only).  step: the forward_backward call the mask belongs to;
+        None = the next call (self.dropout_step).  All True without dropout."""
+        from .dropout import keep_mask
+        assert self.lora is not None, "not a LoRA step"
+        full = next(m for m in LORA_MODULES if m == module or m.split(".")[1] == module)
+        if self.lora.dropout == 0.0:
+            return np.ones((int(rows), int(cols)), dtype=bool)
+        return keep_mask(self.lora.dropout, self.dropout_seed, self.dropout_step if step is None else int(step), self._drop_stream(layer, full), rows, cols)
 
     def _lora_sB(self, l: int, m: str) -> torch.Tensor:
         """scaling * B, [out, Rp]: the operand of the up-projection and of du = dy (scaling B).  Built once per optimiser step for all adapters (one pass over the
@@ -415,13 +464,27 @@ class TrainStep:
 
     def _lora_backward(self, l: int, m: str, dy: torch.Tensor, x: torch.Tensor, u: torch.Tensor, into: Optional[torch.Tensor]) -> torch.Tensor:
         """Gradients of one adapter from dy [rows, out], the linear's input x [rows, in] and the stashed u = x A^T; returns `into` + du A ([rows, in]: the adapter's
-        share of dx).  du = dy (scaling B); dB = scaling dy^T u; dA = du^T x — the two factor gradients on csrc/lora.hip where it takes the shape."""
+        share of dx).  du = dy (scaling B); dB = scaling dy^T u; dA = du^T x — the two factor gradients on csrc/lora.hip where it takes the shape.  With dropout, u is
+        the stashed dropout(x) A^T and x stands for dropout(x) below; nothing masked was stashed."""
         An, Bn = f"model.layers.{l}.{m}.lora_A.weight", f"model.layers.{l}.{m}.lora_B.weight"
         du = self._dgrad(dy, self._lora_sB(l, m))
         if ops.lora_wgrad_ok(dy, u, self.g[Bn]):
             ops.lora_wgrad(dy, u, self.g[Bn], alpha=self.lora.scaling)
         else:                                                # the fp32 verification step, odd shapes: the two-transpose path
             self._wgrad(dy, u * self.lora.scaling, self.g[Bn])
+        if self._drop_on and self.lora.dropout > 0.0:
+            # the adapter saw dropout(x): dA = du^T dropout(x) with the mask regenerated inside the wgrad kernel, and its share of dx is mask * scale * (du A),
+            # added to `into` in fp32 (ops.dropout_add takes every dtype of the step; the first adapter of a chain has nothing to add to).  The elementwise forms
+            # ask only for columns in multiples of 8 and 16-byte aligned rows (ops.dropout_ok), which the hidden / intermediate sizes (multiples of 64, asserted
+            # in __init__) and the step's own buffers always give; there is no other HIP path to fall back to, so anything else is refused here by name.
+            assert ops.dropout_ok(x), "LoRA dropout: the adapter input must have columns in multiples of 8 and 16-byte aligned rows"
+            drop = (*self._drop(), self._drop_stream(l, m))
+            if ops.lora_wgrad_ok(x, du, self.g[An], transposed=True):
+                ops.lora_wgrad_dropout(x, du, *drop, out=self.g[An], transposed=True)
+            else:
+                self._wgrad(du, ops.dropout(x, *drop), self.g[An])
+            t = self._dgrad(du, self.p[An])
+            return ops.dropout(t, *drop, out=t) if into is None else ops.dropout_add(into, t, *drop)
         if ops.lora_wgrad_ok(x, du, self.g[An], transposed=True):
             ops.lora_wgrad(x, du, self.g[An], transposed=True)
         else:
@@ -732,11 +795,19 @@ class TrainStep:
         self._mark_ready(self.proj_names)
 
     def forward_backward(self, input_ids: torch.Tensor, labels: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                         image_features: Optional[torch.Tensor] = None, slot_rows: Optional[Sequence[int]] = None, backward: bool = True):
+                         image_features: Optional[torch.Tensor] = None, slot_rows: Optional[Sequence[int]] = None, backward: bool = True,
+                         dropout: Optional[bool] = None):
         """One micro-batch.  input_ids / labels / attention_mask: [B, L] (ids carry IMAGE_TOKEN_INDEX markers); image_features: output of the
         frozen tower, [n_images, P, mm_hidden] (or a flat [rows, mm_hidden] with slot_rows = rows per image slot).
-        Returns (loss fp32 device scalar, number of counted label positions).  Gradients land in self.g (flat_g)."""
+        Returns (loss fp32 device scalar, number of counted label positions).  Gradients land in self.g (flat_g).
+        dropout (LoraConfig.dropout > 0 only): None = `backward`, i.e. a training call draws its masks and advances self.dropout_step, while a forward-only call
+        is an evaluation in peft's sense (nn.Dropout is the identity in eval mode): no masks, and the counter, hence the masks of later training calls, stays
+        where it is.  True / False force either (a forward-only look at the training loss; a backward through the unmasked adapters)."""
         dev, dt = self.device, self.dtype
+        self._drop_on = bool(backward) if dropout is None else bool(dropout)
+        if self._drop_on:
+            self._drop_step = self.dropout_step                  # one mask set per micro-batch: micro-batches of one accumulation must not share masks
+            self.dropout_step += 1
         if image_features is not None and image_features.dim() == 3:
             slot_rows = [image_features.shape[1]] * image_features.shape[0]
             image_features = image_features.reshape(-1, image_features.shape[-1])

@@ -180,18 +180,19 @@ NON_LORA_PREFIX = "base_model.model."          # PeftModel -> LoraModel -> Llava
 
 
 def save_lora_adapter(output_dir: str, config, *, r: int, lora_alpha: float, target_modules, use_rslora: bool, lora_state: Mapping[str, torch.Tensor],
-                      non_lora_state: Mapping[str, torch.Tensor]) -> str:
+                      non_lora_state: Mapping[str, torch.Tensor], lora_dropout: float = 0.0) -> str:
     """What the reference leaves in output_dir after a LoRA run (llava/train/train.py:987-997: model.config.save_pretrained, model.save_pretrained ->
     peft, torch.save(non_lora_state_dict)):
         adapter_config.json           peft's LoraConfig fields that the loader reads
         adapter_model.safetensors     `base_model.model.model.layers.N.self_attn.q_proj.lora_A.weight` [r, in] / `.lora_B.weight` [out, r] (un-padded)
         non_lora_trainables.bin       the other trained tensors (the projector, ...) as `base_model.model.model.mm_projector.*`
         config.json
-    lora_state: TrainStep.lora_state_dict(); non_lora_state: HF-named tensors (`mm_projector.*` or `model.mm_projector.*`).  Returns the adapter file's path."""
+    lora_state: TrainStep.lora_state_dict(); non_lora_state: HF-named tensors (`mm_projector.*` or `model.mm_projector.*`); lora_dropout: the probability the
+    adapters trained with (a record: merging ignores it).  Returns the adapter file's path."""
     from safetensors.torch import save_file
     os.makedirs(output_dir, exist_ok=True)
     with open(os.path.join(output_dir, "adapter_config.json"), "w") as f:
-        json.dump({"peft_type": "LORA", "task_type": "CAUSAL_LM", "r": int(r), "lora_alpha": lora_alpha, "lora_dropout": 0.0, "bias": "none",
+        json.dump({"peft_type": "LORA", "task_type": "CAUSAL_LM", "r": int(r), "lora_alpha": lora_alpha, "lora_dropout": float(lora_dropout), "bias": "none",
                    "target_modules": sorted(target_modules), "use_rslora": bool(use_rslora), "fan_in_fan_out": False, "modules_to_save": None,
                    "inference_mode": True, "base_model_name_or_path": getattr(config, "_name_or_path", None)}, f, indent=2)
     path = os.path.join(output_dir, "adapter_model.safetensors")
@@ -205,13 +206,14 @@ def save_lora_adapter(output_dir: str, config, *, r: int, lora_alpha: float, tar
 
 
 def train(model_args, data_args, training_args, *, config, weights: MutableMapping[str, torch.Tensor], tokenizer, vision_tower: Optional[Callable] = None,
-          group=None, device="cuda", log: Optional[Callable[[dict], None]] = None) -> Dict[str, object]:
+          group=None, device="cuda", log: Optional[Callable[[dict], None]] = None, allow_lora_dropout: bool = False) -> Dict[str, object]:
     """The reference's train() with the loaded pieces passed in: `config` + `weights` = the language model (HF names; builder.iter_checkpoint reads a
     checkpoint into such a dict), `tokenizer`, `vision_tower` = the frozen tower of the inference model (LlavaLlamaForCausalLM.get_vision_tower(): callable
     on pixel batches, with .image_processor and .hidden_size).  One process per GPU; `group` = the data-parallel group (ZeRO-2 inside TrainStep; every rank
     walks its own stride of the shuffled sample order).  Returns {"losses", "steps", "checkpoint", "state", "frozen", "train_step"}: "state" = the step's state
     dict (with lora_enable: the trained tensors only), "train_step" = the live TrainStep, for callers that go on with it (merged_state_dict(), further steps) — it
-    owns every device buffer of the run, so drop the reference to free them."""
+    owns every device buffer of the run, so drop the reference to free them.  allow_lora_dropout: let a non-zero training_args.lora_dropout (the reference's
+    default is 0.05) reach LoraConfig.dropout, its masks keyed by training_args.seed; False (the default for now) keeps refusing it."""
     from .train import TrainStep
     from .train_data import make_supervised_data_module
     dtype = torch.float16 if training_args.fp16 else (torch.bfloat16 if training_args.bf16 else torch.float32)
@@ -258,7 +260,7 @@ def train(model_args, data_args, training_args, *, config, weights: MutableMappi
     # ---- LoRA (train.py:873-889) and the projector's own rate (llava_trainer.py:150-237) ----------------------------------------------------------------------
     lora = None
     if getattr(training_args, "lora_enable", False):
-        if float(training_args.lora_dropout) != 0.0:
+        if float(training_args.lora_dropout) != 0.0 and not allow_lora_dropout:
             raise NotImplementedError(f"lora_dropout must be 0.0 here (got {training_args.lora_dropout}): LoRA dropout is not implemented")
         if training_args.lora_bias != "none":
             raise NotImplementedError(f"lora_bias must be 'none' (got {training_args.lora_bias!r}): trained LoRA biases are not implemented")
@@ -267,7 +269,7 @@ def train(model_args, data_args, training_args, *, config, weights: MutableMappi
         if model_args.tune_mm_mlp_adapter or model_args.freeze_backbone:
             raise NotImplementedError("lora_enable with tune_mm_mlp_adapter / freeze_backbone is not wired")
         from .train import LoraConfig
-        lora = LoraConfig(r=int(training_args.lora_r), alpha=training_args.lora_alpha)
+        lora = LoraConfig(r=int(training_args.lora_r), alpha=training_args.lora_alpha, dropout=float(training_args.lora_dropout))
     lr_for = None
     if training_args.mm_projector_lr is not None:
         proj_lr, base_lr = float(training_args.mm_projector_lr), float(training_args.learning_rate)
@@ -289,7 +291,7 @@ def train(model_args, data_args, training_args, *, config, weights: MutableMappi
                    lr=training_args.learning_rate, betas=(training_args.adam_beta1, training_args.adam_beta2), eps=training_args.adam_epsilon,
                    weight_decay=training_args.weight_decay, max_grad_norm=training_args.max_grad_norm, group=group,
                    checkpoint=bool(training_args.gradient_checkpointing), max_positions=max(2048, int(tokenizer.model_max_length) + 1024), lora=lora, lr_for=lr_for,
-                   lora_seed=int(training_args.seed))
+                   lora_seed=int(training_args.seed), dropout_seed=int(training_args.seed))
     ts.set_trainable(lambda name: (("model." + name) if name.startswith("mm_projector.") else name) not in frozen)
     gen = torch.Generator().manual_seed(int(training_args.seed))
     sampler = None
@@ -328,7 +330,7 @@ def train(model_args, data_args, training_args, *, config, weights: MutableMappi
         if rank == 0 and training_args.output_dir:
             non_lora = {k: v for k, v in state.items() if k in ts.g and ".lora_" not in k and (("model." + k) if k.startswith("mm_projector.") else k) not in frozen}
             path = save_lora_adapter(training_args.output_dir, config, r=lora.r, lora_alpha=lora.alpha, target_modules=lora.target_modules, use_rslora=lora.use_rslora,
-                                     lora_state=ts.lora_state_dict(), non_lora_state=non_lora)
+                                     lora_state=ts.lora_state_dict(), non_lora_state=non_lora, lora_dropout=lora.dropout)
     else:
         path = save_checkpoint(training_args.output_dir, config, state, model_args) if rank == 0 and training_args.output_dir else None
     if rank == 0 and training_args.output_dir:
