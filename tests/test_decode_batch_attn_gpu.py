@@ -13,6 +13,7 @@ import math
 import pytest
 import torch
 
+import forward_ref as FR
 from test_ops_gpu import DT, TOL, _attn_ref, _fill_cache, _rel_err, _rope_ref, _rope_table
 
 pytestmark = pytest.mark.gpu
@@ -65,7 +66,7 @@ def _check(cuda, dt, n_seq, nh, nkv, garbage, seed=0):
         worst = max(worst, err)
         assert err < TOL[dt], f"sequence {z} (pos {p}): {err:.3e}"
         # the append: rotated k row and the exact v column at `pos`; every other byte of both caches as it was (prefix AND the garbage behind)
-        assert _rel_err(kc[:, p], k_r[0]) < TOL[dt]
+        FR.exact_equal(kc[:, p], FR.rope_chain(src[z, nh * D:(nh + nkv) * D].view(1, nkv, D), p1, table, dt)[0][0], f"sequence {z} (pos {p}): appended key")
         assert torch.equal(vt[:, :, p], v_n[0])
         kb, vb = before[z]
         keep = torch.ones(s_max, dtype=torch.bool, device=cuda); keep[p] = False
