@@ -356,6 +356,22 @@ int lmx_op_transpose(int32_t dtype, const void* src, int32_t ld, int32_t rows, i
 int lmx_op_gemm_wgrad(int32_t dtype, const void* dy, int32_t lddy, const void* x, int32_t ldx, int32_t rows, int32_t out_features, int32_t in_features, void* out,
                       int32_t ldo, void* stream);
 int lmx_op_gemm_wgrad_supported(int32_t dtype, int32_t lddy, int32_t ldx, int32_t rows, int32_t out_features, int32_t in_features, int32_t ldo);
+/* Gradient accumulation (the reference's --gradient_accumulation_steps: HF Trainer back-propagates loss / steps per micro-batch and torch adds into .grad).  The
+ *   accumulating forms ADD to what `out` / `dst` holds instead of overwriting it, inside the kernel that produces the gradient: the prior value joins the fp32
+ *   sum and the result is rounded ONCE, out = T(fp32(out) + new), where torch's `.grad += T(new)` rounds twice; no extra pass over the gradient buffers.
+ * lmx_op_gemm_wgrad_acc: lmx_op_gemm_wgrad's arguments and shape rule (lmx_op_gemm_wgrad_supported); out[o][i] = T(fp32(out[o][i]) + sum_r dy[r][o] * x[r][i]),
+ *   bit-identical to lmx_op_gemm on the transposed operands with residual = out.
+ * lmx_op_lora_wgrad_acc / lmx_op_lora_wgrad_dropout_acc: the arguments, shapes, workspace and determinism of lmx_op_lora_wgrad / lmx_op_lora_wgrad_dropout (below);
+ *   out = T(alpha * sum + fp32(out)) for the R_out stored columns, nothing else of `out` is read or written.
+ * lmx_op_cast_f32_add: dst[i] = T(fp32(dst[i]) + src[i]), fp32 / bf16 / f16 (the norm-weight, bias and embedding-table gradients, which come out of fp32 buffers). */
+int lmx_op_gemm_wgrad_acc(int32_t dtype, const void* dy, int32_t lddy, const void* x, int32_t ldx, int32_t rows, int32_t out_features, int32_t in_features, void* out,
+                          int32_t ldo, void* stream);
+int lmx_op_lora_wgrad_acc(int32_t dtype, const void* big, int32_t ld_big, const void* small, int32_t ld_small, int32_t rows, int32_t F, int32_t R, int32_t R_out,
+                          float alpha, int32_t transposed, int32_t n_slices, void* out, int32_t ld_out, void* workspace, size_t workspace_bytes, void* stream);
+int lmx_op_lora_wgrad_dropout_acc(int32_t dtype, const void* big, int32_t ld_big, const void* small, int32_t ld_small, int32_t rows, int32_t F, int32_t R,
+                                  int32_t R_out, float alpha, int32_t transposed, int32_t n_slices, void* out, int32_t ld_out, void* workspace,
+                                  size_t workspace_bytes, double p, uint64_t seed, uint32_t step, uint32_t stream_id, void* stream);
+int lmx_op_cast_f32_add(int32_t dtype, const float* src, void* dst, int64_t n, void* stream);
 /* lmx_op_lora_wgrad: the gradient of one LoRA factor (peft's lora_A / lora_B are nn.Linear modules: grad_weight = grad_output^T @ input under
  *   llava/train/train.py:873-889), out = T(alpha * sum_{row < rows} big[row][f] * small[row][j]) with both operands in their forward layout: big [rows][ld_big]
  *   (F columns read: dy for lora_B, the layer input for lora_A), small [rows][ld_small] (R columns read: x A^T or dy B, R = the rank padded to a multiple of 64).

@@ -668,7 +668,13 @@ int lmx_op_transpose(int32_t dtype, const void* src, int32_t ld, int32_t rows, i
 int lmx_op_gemm_wgrad(int32_t dtype, const void* dy, int32_t lddy, const void* x, int32_t ldx, int32_t rows, int32_t out_features, int32_t in_features, void* out,
                       int32_t ldo, void* stream) {
     LMX_API_BEGIN
-    launch_gemm_wgrad(dtype, dy, lddy, x, ldx, rows, out_features, in_features, out, ldo, S(stream));
+    launch_gemm_wgrad(dtype, dy, lddy, x, ldx, rows, out_features, in_features, out, ldo, false, S(stream));
+    LMX_API_END
+}
+int lmx_op_gemm_wgrad_acc(int32_t dtype, const void* dy, int32_t lddy, const void* x, int32_t ldx, int32_t rows, int32_t out_features, int32_t in_features, void* out,
+                          int32_t ldo, void* stream) {
+    LMX_API_BEGIN
+    launch_gemm_wgrad(dtype, dy, lddy, x, ldx, rows, out_features, in_features, out, ldo, true, S(stream));
     LMX_API_END
 }
 int lmx_op_gemm_wgrad_supported(int32_t dtype, int32_t lddy, int32_t ldx, int32_t rows, int32_t out_features, int32_t in_features, int32_t ldo) {
@@ -677,7 +683,13 @@ int lmx_op_gemm_wgrad_supported(int32_t dtype, int32_t lddy, int32_t ldx, int32_
 int lmx_op_lora_wgrad(int32_t dtype, const void* big, int32_t ld_big, const void* small, int32_t ld_small, int32_t rows, int32_t F, int32_t R, int32_t R_out,
                       float alpha, int32_t transposed, int32_t n_slices, void* out, int32_t ld_out, void* workspace, size_t workspace_bytes, void* stream) {
     LMX_API_BEGIN
-    launch_lora_wgrad(dtype, big, ld_big, small, ld_small, rows, F, R, R_out, alpha, transposed, n_slices, out, ld_out, workspace, workspace_bytes, S(stream));
+    launch_lora_wgrad(dtype, big, ld_big, small, ld_small, rows, F, R, R_out, alpha, transposed, n_slices, out, ld_out, workspace, workspace_bytes, false, S(stream));
+    LMX_API_END
+}
+int lmx_op_lora_wgrad_acc(int32_t dtype, const void* big, int32_t ld_big, const void* small, int32_t ld_small, int32_t rows, int32_t F, int32_t R, int32_t R_out,
+                          float alpha, int32_t transposed, int32_t n_slices, void* out, int32_t ld_out, void* workspace, size_t workspace_bytes, void* stream) {
+    LMX_API_BEGIN
+    launch_lora_wgrad(dtype, big, ld_big, small, ld_small, rows, F, R, R_out, alpha, transposed, n_slices, out, ld_out, workspace, workspace_bytes, true, S(stream));
     LMX_API_END
 }
 int lmx_op_lora_wgrad_supported(int32_t dtype, int32_t ld_big, int32_t ld_small, int32_t rows, int32_t F, int32_t R, int32_t R_out, int32_t transposed,
@@ -693,7 +705,15 @@ int lmx_op_lora_wgrad_dropout(int32_t dtype, const void* big, int32_t ld_big, co
                               uint64_t seed, uint32_t step, uint32_t stream_id, void* stream) {
     LMX_API_BEGIN
     launch_lora_wgrad_dropout(dtype, big, ld_big, small, ld_small, rows, F, R, R_out, alpha, transposed, n_slices, out, ld_out, workspace, workspace_bytes, p, seed,
-                              step, stream_id, S(stream));
+                              step, stream_id, false, S(stream));
+    LMX_API_END
+}
+int lmx_op_lora_wgrad_dropout_acc(int32_t dtype, const void* big, int32_t ld_big, const void* small, int32_t ld_small, int32_t rows, int32_t F, int32_t R,
+                                  int32_t R_out, float alpha, int32_t transposed, int32_t n_slices, void* out, int32_t ld_out, void* workspace,
+                                  size_t workspace_bytes, double p, uint64_t seed, uint32_t step, uint32_t stream_id, void* stream) {
+    LMX_API_BEGIN
+    launch_lora_wgrad_dropout(dtype, big, ld_big, small, ld_small, rows, F, R, R_out, alpha, transposed, n_slices, out, ld_out, workspace, workspace_bytes, p, seed,
+                              step, stream_id, true, S(stream));
     LMX_API_END
 }
 int lmx_op_lora_down_dropout(int32_t dtype, const void* x, int32_t ldx, const void* A, int32_t lda, void* u, int32_t ldu, int32_t rows, int32_t K, int32_t Rp, int32_t G,
@@ -746,7 +766,12 @@ int lmx_op_elementwise(int32_t dtype, int32_t op, const void* a, const void* b, 
 }
 int lmx_op_cast_f32(int32_t dtype, const float* src, void* dst, int64_t n, void* stream) {
     LMX_API_BEGIN
-    launch_cast_f32(dtype, src, dst, (size_t)n, S(stream));
+    launch_cast_f32(dtype, src, dst, (size_t)n, false, S(stream));
+    LMX_API_END
+}
+int lmx_op_cast_f32_add(int32_t dtype, const float* src, void* dst, int64_t n, void* stream) {
+    LMX_API_BEGIN
+    launch_cast_f32(dtype, src, dst, (size_t)n, true, S(stream));
     LMX_API_END
 }
 int lmx_op_col_sum(int32_t dtype, const void* dy, int32_t ld, int32_t rows, int32_t cols, float* out, void* stream) {

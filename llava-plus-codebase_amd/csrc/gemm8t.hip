@@ -22,6 +22,11 @@
 //     row-major [r][256 columns] image would be 4-way conflicted, 8.0).
 // Shapes: M % 256 == 0, N % 256 == 0, rows % 64 == 0, row strides multiples of 8 elements (the launcher checks; the training step falls back to the transposes
 // otherwise).  Results are bit-identical to transposes + gemm8p: same MFMA, same values in the same contraction slots, same K-step order.
+//
+// ACC (gradient accumulation: micro-batch i > 0 of an optimiser step): C = T(fp32(C) + sum) — the prior gradient joins the fp32 accumulator before the ONE rounding,
+// as the forward GEMM's residual epilogue does (gemm_common.h: v += r; store4), where a separate `grad += new` pass would round twice and read and write every
+// gradient once more.  The epilogue loads the 4 prior elements a lane is about to overwrite with the store's own (m, n, ldc) addressing, a whole W half (16
+// quads per lane = 32 registers, free once the fragments are dead) ahead of that half's first store.  The non-accumulating instantiations are the code they were.
 #include <mutex>
 
 #include "common.h"
@@ -54,7 +59,7 @@ __device__ __forceinline__ v4i_t make_rsrc(const void* p, uint32_t bytes) {
 
 }  // namespace
 
-template <typename T>
+template <typename T, bool ACC>
 __global__ __launch_bounds__(512) void gemm8t_kernel(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -213,17 +218,34 @@ __global__ __launch_bounds__(512) void gemm8t_kernel(GemmArgs a) {
     // ---- epilogue: acc[i][j][4 q + e] = C[m0 + (j >> 1) * 128 + wm * 64 + (j & 1) * 32 + l31][n0 + i * 128 + wn * 32 + 8 q + 4 hi + e] -----------------
     T* __restrict__ C = reinterpret_cast<T*>(a.C);
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i) {
+        uint2 prior[ACC ? 4 : 1][4];
+        if constexpr (ACC) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int m = m0 + (j >> 1) * 128 + wm * 64 + (j & 1) * 32 + l31;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int n = n0 + i * 128 + wn * 32 + 8 * q + 4 * hi;
+                    prior[j][q] = *reinterpret_cast<const uint2*>(C + (size_t)m * a.ldc + n);
+                }
+            }
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int m = m0 + (j >> 1) * 128 + wm * 64 + (j & 1) * 32 + l31;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int n = n0 + i * 128 + wn * 32 + 8 * q + 4 * hi;
-                const float v[4] = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
+                float v[4] = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
+                if constexpr (ACC) {
+                    v[0] += unpack_lo<T>(prior[j][q].x); v[1] += unpack_hi<T>(prior[j][q].x);
+                    v[2] += unpack_lo<T>(prior[j][q].y); v[3] += unpack_hi<T>(prior[j][q].y);
+                }
                 store4<T>(C + (size_t)m * a.ldc + n, v);
             }
         }
+    }
 }
 
 bool gemm_wgrad_direct_ok(int dtype, int M, int N, int rows, int ldx, int ldw, int ldc) {
@@ -231,7 +253,7 @@ bool gemm_wgrad_direct_ok(int dtype, int M, int N, int rows, int ldx, int ldw, i
            ldc % 4 == 0 && ldx >= M && ldw >= N && ldc >= N && (size_t)rows * ldx * 2 < ((size_t)1 << 32) && (size_t)rows * ldw * 2 < ((size_t)1 << 32);
 }
 
-void launch_gemm_wgrad(int dtype, const void* dy, int lddy, const void* x, int ldx, int rows, int M, int N, void* out, int ldo, hipStream_t st) {
+void launch_gemm_wgrad(int dtype, const void* dy, int lddy, const void* x, int ldx, int rows, int M, int N, void* out, int ldo, bool accumulate, hipStream_t st) {
     dispatch_dtype16(dtype, "gemm_wgrad", [&](auto t) {      // first: the shape rule below would report a bad dtype code as a bad shape
         LMX_REQUIRE(gemm_wgrad_direct_ok(dtype, M, N, rows, lddy, ldx, ldo),
                     "gemm_wgrad: 16-bit operands, out features and in features multiples of 256, rows a multiple of 64, 16-byte aligned row strides, operands below 4 GiB");
@@ -239,12 +261,15 @@ void launch_gemm_wgrad(int dtype, const void* dy, int lddy, const void* x, int l
         GemmArgs a{};
         a.X = dy; a.W = x; a.C = out; a.M = M; a.N = N; a.K = rows; a.ldx = lddy; a.ldw = ldx; a.ldc = ldo;
         const int tiles = (M >> 8) * (N >> 8);
-        static std::once_flag once;                       // both instantiations decay to the same pointer type: opt both in at once
+        static std::once_flag once;                       // the instantiations decay to the same pointer type: opt all in at once
         std::call_once(once, [] {
-            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8t_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS));
-            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8t_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS));
+            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8t_kernel<bf16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS));
+            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8t_kernel<f16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS));
+            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8t_kernel<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS));
+            LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8t_kernel<f16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, T8_LDS));
         });
-        LMX_LAUNCH(gemm8t_kernel<LMX_T(t)>, dim3(tiles), dim3(512), T8_LDS, st, a);
+        if (accumulate) LMX_LAUNCH((gemm8t_kernel<LMX_T(t), true>), dim3(tiles), dim3(512), T8_LDS, st, a);
+        else LMX_LAUNCH((gemm8t_kernel<LMX_T(t), false>), dim3(tiles), dim3(512), T8_LDS, st, a);
         LMX_CHECK_HIP(hipGetLastError());
     });
 }

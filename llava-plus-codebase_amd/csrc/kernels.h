@@ -354,20 +354,21 @@ void launch_rmsnorm_bwd(int dtype, const void* x, const void* w, const void* dy,
 void launch_swiglu_bwd(int dtype, const void* g, const void* u, const void* dact, void* dg, void* du, size_t n, hipStream_t st);
 void launch_rope_bwd(int dtype, const void* dy, void* dx, const float* cos_sin, int pos0, int Tn, int heads, int D, int ld, hipStream_t st);
 void launch_transpose(int dtype, const void* src, int ld, int rows, int cols, void* dst, int ldd, hipStream_t st);
-// gemm8t.hip: out[M][N] = sum_r dy[r][m] * x[r][n] with both operands in their forward layout (no transposes); gemm_wgrad_direct_ok = the shapes it takes
+// gemm8t.hip: out[M][N] = sum_r dy[r][m] * x[r][n] with both operands in their forward layout (no transposes); gemm_wgrad_direct_ok = the shapes it takes.
+// accumulate (here and in the LoRA launchers below): out = T(fp32(out) + the product), the prior added before the one rounding (gradient accumulation)
 bool gemm_wgrad_direct_ok(int dtype, int M, int N, int rows, int lddy, int ldx, int ldo);
-void launch_gemm_wgrad(int dtype, const void* dy, int lddy, const void* x, int ldx, int rows, int M, int N, void* out, int ldo, hipStream_t st);
+void launch_gemm_wgrad(int dtype, const void* dy, int lddy, const void* x, int ldx, int rows, int M, int N, void* out, int ldo, bool accumulate, hipStream_t st);
 // lora.hip: out = T(alpha * sum_r big[r][f] * small[r][j]) for a LoRA factor, [F][R_out] or transposed [R_out][F]; both operands in their forward layout, the
 // rows split into slices whose fp32 partials (workspace) are summed in slice order.  lora_wgrad_ok = the shapes it takes; n_slices 0 = automatic
 bool lora_wgrad_ok(int dtype, int ld_big, int ld_small, int rows, int F, int R, int R_out, int transposed, int ld_out);
 int lora_wgrad_slices(int rows, int F, int n_slices);
 size_t lora_wgrad_workspace_bytes(int rows, int F, int R, int n_slices);
 void launch_lora_wgrad(int dtype, const void* big, int ld_big, const void* small, int ld_small, int rows, int F, int R, int R_out, float alpha, int transposed,
-                       int n_slices, void* out, int ld_out, void* workspace, size_t workspace_bytes, hipStream_t st);
+                       int n_slices, void* out, int ld_out, void* workspace, size_t workspace_bytes, bool accumulate, hipStream_t st);
 // the same product with the LoRA dropout mask (dropout.h) applied to `big` in registers, rows counted from the operand's first row: dA = du^T dropout(x)
 void launch_lora_wgrad_dropout(int dtype, const void* big, int ld_big, const void* small, int ld_small, int rows, int F, int R, int R_out, float alpha,
                                int transposed, int n_slices, void* out, int ld_out, void* workspace, size_t workspace_bytes, double p, uint64_t seed, uint32_t step,
-                               uint32_t stream, hipStream_t st);
+                               uint32_t stream, bool accumulate, hipStream_t st);
 // lora.hip: u[:, g Rp .. (g + 1) Rp) = dropout_g(x) A_g^T for the G <= 3 adapters that share the input x (A [G Rp][K], adapter g on stream stream0 + g); the mask is
 // applied to x's chunks in registers, no masked copy of x leaves the chip.  lora_down_dropout_ok = the shapes it takes
 bool lora_down_dropout_ok(int dtype, int ldx, int lda, int ldu, int rows, int K, int Rp, int G);
@@ -385,7 +386,7 @@ void launch_attn_bwd_mfma(int dtype, int D, const void* q, const void* k, const 
 void launch_attn_bwd(int dtype, int D, const void* q, const void* k, const void* v, const void* dO, void* dq, float* dk32, float* dv32, void* dk, void* dv,
                      int Tn, int heads, int kv_heads, int ldq, int ldk, int ldo, float scale, hipStream_t st);
 void launch_elementwise(int dtype, int op, const void* a, const void* b, void* out, size_t n, hipStream_t st);       // 0 swiglu, 1 gelu, 2 gelu_bwd, 3 add
-void launch_cast_f32(int dtype, const float* src, void* dst, size_t n, hipStream_t st);
+void launch_cast_f32(int dtype, const float* src, void* dst, size_t n, bool accumulate, hipStream_t st);      // accumulate: dst = T(fp32(dst) + src)
 void launch_col_sum(int dtype, const void* dy, int ld, int rows, int cols, float* out, hipStream_t st);
 void launch_embed_bwd(int dtype, const int* src, const void* d, float* dtable, void* dfeats, int rows, int H, hipStream_t st);
 void launch_sumsq(int dtype, const void* x, size_t n, float* acc, hipStream_t st);

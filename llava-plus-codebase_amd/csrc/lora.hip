@@ -18,6 +18,8 @@
 //
 // Reduction: each workgroup writes its fp32 partial tile to workspace[slice][F][R]; a second launch sums the slices IN SLICE ORDER, applies alpha, rounds once
 // and stores [F][R_out] or, transposed, [R_out][F] (columns R_out .. R - 1 are padding and are dropped).  No atomics: same inputs, same bits.
+// Gradient accumulation (micro-batch i > 0 of an optimiser step): the reducer adds what `out` holds, in fp32, before that one rounding:
+// out = T(alpha * sum + fp32(out)); the element is read by the thread that then stores it.
 //
 // LoRA dropout (dropout.h: peft's lora_A(dropout(x)), p = 0.05 in the reference's scripts).  The mask is a function of (row, column group, stream, step), so no
 // masked copy of x exists anywhere: lora_wgrad_drop_kernel applies mask and scale to the big operand's chunks in registers on their way to LDS
@@ -291,10 +293,11 @@ __global__ __launch_bounds__(LW_THREADS) void lora_down_dropout_kernel(LoraDownA
         }
 }
 
-// out = T(alpha * (ws[0] + ws[1] + ... + ws[S - 1])), 32 (f) x 32 (r) per workgroup; the transposed store goes through LDS so that both sides run along rows
+// out = T(alpha * (ws[0] + ws[1] + ... + ws[S - 1]) (+ fp32(out) when accumulate)), 32 (f) x 32 (r) per workgroup; the transposed store goes through LDS so that
+// both sides run along rows
 template <typename T, bool TRANSPOSED>
 __global__ __launch_bounds__(256) void lora_wgrad_reduce_kernel(const float* __restrict__ ws, int S, int F, int R, int R_out, float alpha, T* __restrict__ out,
-                                                                int ld_out) {
+                                                                int ld_out, int accumulate) {
     __shared__ float tile[32][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int f0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
@@ -306,14 +309,21 @@ __global__ __launch_bounds__(256) void lora_wgrad_reduce_kernel(const float* __r
             for (int sl = 0; sl < S; ++sl) s += ws[((size_t)sl * F + f) * R + r];
         s *= alpha;
         if constexpr (TRANSPOSED) tile[fl][tx] = s;
-        else if (r < R_out) out[(size_t)f * ld_out + r] = from_f32<T>(s);
+        else if (r < R_out) {
+            if (accumulate) s += to_f32(out[(size_t)f * ld_out + r]);
+            out[(size_t)f * ld_out + r] = from_f32<T>(s);
+        }
     }
     if constexpr (TRANSPOSED) {
         __syncthreads();
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             const int rl = ty + 8 * p, r = r0 + rl;
-            if (r < R_out) out[(size_t)r * ld_out + f0 + tx] = from_f32<T>(tile[tx][rl]);
+            if (r < R_out) {
+                float s = tile[tx][rl];
+                if (accumulate) s += to_f32(out[(size_t)r * ld_out + f0 + tx]);
+                out[(size_t)r * ld_out + f0 + tx] = from_f32<T>(s);
+            }
         }
     }
 }
@@ -373,7 +383,7 @@ void opt_in_large_lds() {
 
 // drop = null: the plain product; else the mask of *drop on the big operand
 void lora_wgrad_impl(int dtype, const void* big, int ld_big, const void* small, int ld_small, int rows, int F, int R, int R_out, float alpha, int transposed,
-                     int n_slices, void* out, int ld_out, void* workspace, size_t workspace_bytes, const DropSpec* drop, hipStream_t st) {
+                     int n_slices, void* out, int ld_out, void* workspace, size_t workspace_bytes, const DropSpec* drop, bool accumulate, hipStream_t st) {
     dispatch_dtype16(dtype, "lora_wgrad", [&](auto t) {      // first: the shape rule below would report a bad dtype code as a bad shape
         using T = LMX_T(t);
         LMX_REQUIRE(lora_wgrad_ok(dtype, ld_big, ld_small, rows, F, R, R_out, transposed, ld_out),
@@ -407,8 +417,8 @@ void lora_wgrad_impl(int dtype, const void* big, int ld_big, const void* small, 
         LMX_CHECK_HIP(hipGetLastError());
         const dim3 rgrid((unsigned)(F / 32), (unsigned)cdiv(R_out, 32));
         T* o = reinterpret_cast<T*>(out);
-        if (transposed) hipLaunchKernelGGL((lora_wgrad_reduce_kernel<T, true>), rgrid, dim3(256), 0, st, a.ws, S, F, R, R_out, alpha, o, ld_out);
-        else hipLaunchKernelGGL((lora_wgrad_reduce_kernel<T, false>), rgrid, dim3(256), 0, st, a.ws, S, F, R, R_out, alpha, o, ld_out);
+        if (transposed) hipLaunchKernelGGL((lora_wgrad_reduce_kernel<T, true>), rgrid, dim3(256), 0, st, a.ws, S, F, R, R_out, alpha, o, ld_out, (int)accumulate);
+        else hipLaunchKernelGGL((lora_wgrad_reduce_kernel<T, false>), rgrid, dim3(256), 0, st, a.ws, S, F, R, R_out, alpha, o, ld_out, (int)accumulate);
         LMX_CHECK_HIP(hipGetLastError());
     });
 }
@@ -416,16 +426,16 @@ void lora_wgrad_impl(int dtype, const void* big, int ld_big, const void* small, 
 }  // namespace
 
 void launch_lora_wgrad(int dtype, const void* big, int ld_big, const void* small, int ld_small, int rows, int F, int R, int R_out, float alpha, int transposed,
-                       int n_slices, void* out, int ld_out, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    lora_wgrad_impl(dtype, big, ld_big, small, ld_small, rows, F, R, R_out, alpha, transposed, n_slices, out, ld_out, workspace, workspace_bytes, nullptr, st);
+                       int n_slices, void* out, int ld_out, void* workspace, size_t workspace_bytes, bool accumulate, hipStream_t st) {
+    lora_wgrad_impl(dtype, big, ld_big, small, ld_small, rows, F, R, R_out, alpha, transposed, n_slices, out, ld_out, workspace, workspace_bytes, nullptr, accumulate, st);
 }
 
 void launch_lora_wgrad_dropout(int dtype, const void* big, int ld_big, const void* small, int ld_small, int rows, int F, int R, int R_out, float alpha,
                                int transposed, int n_slices, void* out, int ld_out, void* workspace, size_t workspace_bytes, double p, uint64_t seed, uint32_t step,
-                               uint32_t stream, hipStream_t st) {
+                               uint32_t stream, bool accumulate, hipStream_t st) {
     LMX_REQUIRE(p >= 0.0 && p < 1.0, "lora_wgrad_dropout: p must be in [0, 1)");
     const DropSpec d = make_drop_spec(p, seed, step, stream);
-    lora_wgrad_impl(dtype, big, ld_big, small, ld_small, rows, F, R, R_out, alpha, transposed, n_slices, out, ld_out, workspace, workspace_bytes, &d, st);
+    lora_wgrad_impl(dtype, big, ld_big, small, ld_small, rows, F, R, R_out, alpha, transposed, n_slices, out, ld_out, workspace, workspace_bytes, &d, accumulate, st);
 }
 
 bool lora_down_dropout_ok(int dtype, int ldx, int lda, int ldu, int rows, int K, int Rp, int G) {

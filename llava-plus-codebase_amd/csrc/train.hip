@@ -609,6 +609,14 @@ __global__ __launch_bounds__(256) void cast_f32_kernel(const float* __restrict__
     if (i < n) dst[i] = from_f32<T>(src[i]);
 }
 
+// gradient accumulation of the tensors whose gradient comes out of an fp32 buffer (norm weights, projector biases, the embedding table): dst = T(fp32(dst) + src),
+// the prior joins in fp32 before the one rounding
+template <typename T>
+__global__ __launch_bounds__(256) void cast_f32_add_kernel(const float* __restrict__ src, T* __restrict__ dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = from_f32<T>(to_f32(dst[i]) + src[i]);
+}
+
 void launch_attn_bwd(int dtype, int D, const void* q, const void* k, const void* v, const void* dO, void* dq, float* dk32, float* dv32, void* dk, void* dv,
                      int Tn, int heads, int kv_heads, int ldq, int ldk, int ldo, float scale, hipStream_t st) {
     LMX_REQUIRE(D == 64 || D == 128, "attn_bwd: head_dim must be 64 or 128");
@@ -719,10 +727,12 @@ void launch_elementwise(int dtype, int op, const void* a, const void* b, void* o
     LMX_CHECK_HIP(hipGetLastError());
 }
 
-void launch_cast_f32(int dtype, const float* src, void* dst, size_t n, hipStream_t st) {
+void launch_cast_f32(int dtype, const float* src, void* dst, size_t n, bool accumulate, hipStream_t st) {
     if (!n) return;
-    dispatch_dtype(dtype, "cast_f32", [&](auto t) {
-        hipLaunchKernelGGL(cast_f32_kernel<LMX_T(t)>, dim3((unsigned)cdiv64((int64_t)n, 256)), dim3(256), 0, st, src, (LMX_T(t)*)dst, n);
+    dispatch_dtype(dtype, accumulate ? "cast_f32_add" : "cast_f32", [&](auto t) {
+        const dim3 grid((unsigned)cdiv64((int64_t)n, 256));
+        if (accumulate) hipLaunchKernelGGL(cast_f32_add_kernel<LMX_T(t)>, grid, dim3(256), 0, st, src, (LMX_T(t)*)dst, n);
+        else hipLaunchKernelGGL(cast_f32_kernel<LMX_T(t)>, grid, dim3(256), 0, st, src, (LMX_T(t)*)dst, n);
     });
     LMX_CHECK_HIP(hipGetLastError());
 }

@@ -133,9 +133,14 @@ _SIGS = {
     "lmx_op_rope_bwd": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "lmx_op_transpose": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
     "lmx_op_gemm_wgrad": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "lmx_op_gemm_wgrad_acc": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
     "lmx_op_gemm_wgrad_supported": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     "lmx_op_lora_wgrad": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p, c_int32,
                                     c_void_p, c_size_t, c_void_p]),
+    "lmx_op_lora_wgrad_acc": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p, c_int32,
+                                        c_void_p, c_size_t, c_void_p]),
+    "lmx_op_lora_wgrad_dropout_acc": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p,
+                                                c_int32, c_void_p, c_size_t, c_double, c_uint64, c_uint32, c_uint32, c_void_p]),
     "lmx_op_lora_wgrad_supported": (c_int32, [c_int32] * 9),
     "lmx_op_lora_wgrad_workspace": (c_size_t, [c_int32] * 4),
     "lmx_op_lora_wgrad_dropout": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p,
@@ -149,6 +154,7 @@ _SIGS = {
     "lmx_dropout_keep_host": (c_int32, [c_double, c_uint64, c_uint32, c_uint32, c_int32, c_int32, c_void_p]),
     "lmx_op_elementwise": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "lmx_op_cast_f32": (c_int32, [c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "lmx_op_cast_f32_add": (c_int32, [c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     "lmx_op_col_sum": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "lmx_op_gather_embed": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "lmx_op_embed_bwd": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),

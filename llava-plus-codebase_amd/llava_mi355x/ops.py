@@ -331,11 +331,12 @@ def elementwise(op, a, b=None, out=None):
     return out
 
 
-def cast_f32(src, out):
-    """fp32 accumulator -> `out` (parameter dtype), same number of elements."""
+def cast_f32(src, out, accumulate=False):
+    """fp32 accumulator -> `out` (parameter dtype), same number of elements.  accumulate: out = T(fp32(out) + src), one rounding (gradient accumulation)."""
     _need_cuda(src, out)
     assert src.dtype == torch.float32 and src.numel() == out.numel() and src.is_contiguous() and out.is_contiguous()
-    check(lib.lmx_op_cast_f32(torch_dtype_code(out.dtype), ptr(src), ptr(out), src.numel(), stream_handle()), "cast_f32")
+    fn = lib.lmx_op_cast_f32_add if accumulate else lib.lmx_op_cast_f32
+    check(fn(torch_dtype_code(out.dtype), ptr(src), ptr(out), src.numel(), stream_handle()), "cast_f32_add" if accumulate else "cast_f32")
     return out
 
 
@@ -396,12 +397,14 @@ def wgrad_direct_ok(dy, x, out):
     return bool(lib.lmx_op_gemm_wgrad_supported(torch_dtype_code(dy.dtype), dy.stride(0), x.stride(0), dy.shape[0], dy.shape[1], x.shape[1], out.stride(0)))
 
 
-def gemm_wgrad(dy, x, out):
-    """out [O, I] = dy[R, O]^T @ x[R, I] with both operands in their forward layout (csrc/gemm8t.hip); fails loudly on shapes wgrad_direct_ok rejects."""
+def gemm_wgrad(dy, x, out, accumulate=False):
+    """out [O, I] = dy[R, O]^T @ x[R, I] with both operands in their forward layout (csrc/gemm8t.hip); fails loudly on shapes wgrad_direct_ok rejects.
+    accumulate: out = T(fp32(out) + the product), the prior added to the fp32 sum before the one rounding (gradient accumulation)."""
     _need_cuda_rows(dy, x, out)
     assert dy.shape[0] == x.shape[0] and tuple(out.shape) == (dy.shape[1], x.shape[1])
-    check(lib.lmx_op_gemm_wgrad(torch_dtype_code(dy.dtype), ptr(dy), dy.stride(0), ptr(x), x.stride(0), dy.shape[0], dy.shape[1], x.shape[1], ptr(out), out.stride(0),
-                                stream_handle()), "gemm_wgrad")
+    fn = lib.lmx_op_gemm_wgrad_acc if accumulate else lib.lmx_op_gemm_wgrad
+    check(fn(torch_dtype_code(dy.dtype), ptr(dy), dy.stride(0), ptr(x), x.stride(0), dy.shape[0], dy.shape[1], x.shape[1], ptr(out), out.stride(0), stream_handle()),
+          "gemm_wgrad_acc" if accumulate else "gemm_wgrad")
     return out
 
 
@@ -416,9 +419,10 @@ def lora_wgrad_ok(big, small, out, r_out=None, transposed=False):
                                                 int(transposed), out.stride(0)))
 
 
-def lora_wgrad(big, small, out=None, alpha=1.0, r_out=None, transposed=False, n_slices=0):
+def lora_wgrad(big, small, out=None, alpha=1.0, r_out=None, transposed=False, n_slices=0, accumulate=False):
     """out = alpha * big[rows, F]^T @ small[rows, R][:, :r_out], stored [F, r_out] or, transposed, [r_out, F]; both operands in their forward layout
-    (csrc/lora.hip).  The gradient of a LoRA factor: (dy, u) -> dB, (x, du) transposed -> dA.  Fails loudly on shapes lora_wgrad_ok rejects."""
+    (csrc/lora.hip).  The gradient of a LoRA factor: (dy, u) -> dB, (x, du) transposed -> dA.  Fails loudly on shapes lora_wgrad_ok rejects.
+    accumulate: out = T(alpha * product + fp32(out)), one rounding (gradient accumulation: `out` holds the prior)."""
     _need_cuda_rows(big, small, out)
     rows, F = big.shape
     R = small.shape[1]
@@ -429,8 +433,9 @@ def lora_wgrad(big, small, out=None, alpha=1.0, r_out=None, transposed=False, n_
     assert small.shape[0] == rows and tuple(out.shape) == shape and out.dtype == big.dtype == small.dtype
     nbytes = int(lib.lmx_op_lora_wgrad_workspace(rows, F, R, n_slices))
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=big.device)
-    check(lib.lmx_op_lora_wgrad(torch_dtype_code(big.dtype), ptr(big), big.stride(0), ptr(small), small.stride(0), rows, F, R, r_out, float(alpha), int(transposed),
-                                int(n_slices), ptr(out), out.stride(0), ptr(ws), nbytes, stream_handle()), "lora_wgrad")
+    fn = lib.lmx_op_lora_wgrad_acc if accumulate else lib.lmx_op_lora_wgrad
+    check(fn(torch_dtype_code(big.dtype), ptr(big), big.stride(0), ptr(small), small.stride(0), rows, F, R, r_out, float(alpha), int(transposed),
+             int(n_slices), ptr(out), out.stride(0), ptr(ws), nbytes, stream_handle()), "lora_wgrad_acc" if accumulate else "lora_wgrad")
     return out
 
 
@@ -500,8 +505,9 @@ def lora_down_dropout(x, A_stack, G, p, seed, step, stream0, out=None):
     return out
 
 
-def lora_wgrad_dropout(big, small, p, seed, step, stream, out=None, alpha=1.0, r_out=None, transposed=False, n_slices=0):
-    """lora_wgrad with the LoRA dropout mask applied to `big` inside the kernel: dA = du^T dropout(x) for (x, du), transposed.  Takes what lora_wgrad_ok takes."""
+def lora_wgrad_dropout(big, small, p, seed, step, stream, out=None, alpha=1.0, r_out=None, transposed=False, n_slices=0, accumulate=False):
+    """lora_wgrad with the LoRA dropout mask applied to `big` inside the kernel: dA = du^T dropout(x) for (x, du), transposed.  Takes what lora_wgrad_ok takes.
+    accumulate: as lora_wgrad."""
     _need_cuda_rows(big, small, out)
     rows, F = big.shape
     R = small.shape[1]
@@ -513,9 +519,9 @@ def lora_wgrad_dropout(big, small, p, seed, step, stream, out=None, alpha=1.0, r
     p, seed, step, stream = _drop_args(p, seed, step, stream)
     nbytes = int(lib.lmx_op_lora_wgrad_workspace(rows, F, R, n_slices))
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=big.device)
-    check(lib.lmx_op_lora_wgrad_dropout(torch_dtype_code(big.dtype), ptr(big), big.stride(0), ptr(small), small.stride(0), rows, F, R, r_out, float(alpha),
-                                        int(transposed), int(n_slices), ptr(out), out.stride(0), ptr(ws), nbytes, p, seed, step, stream, stream_handle()),
-          "lora_wgrad_dropout")
+    fn = lib.lmx_op_lora_wgrad_dropout_acc if accumulate else lib.lmx_op_lora_wgrad_dropout
+    check(fn(torch_dtype_code(big.dtype), ptr(big), big.stride(0), ptr(small), small.stride(0), rows, F, R, r_out, float(alpha), int(transposed), int(n_slices),
+             ptr(out), out.stride(0), ptr(ws), nbytes, p, seed, step, stream, stream_handle()), "lora_wgrad_dropout_acc" if accumulate else "lora_wgrad_dropout")
     return out
 
 

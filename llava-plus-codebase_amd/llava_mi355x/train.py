@@ -21,6 +21,12 @@ This is the parity-first version: fp32-engine runs match torch autograd + torch.
 `checkpoint=True` keeps only each layer's input and recomputes the layer in the backward pass (the reference's gradient_checkpointing).
 `keep_layers` / `keep_budget_bytes` (round 6): with 288 GB per GPU the LAST k layers keep their activations anyway — as many as the budget holds — and are
 not recomputed: every kept layer takes one forward (a quarter of its GEMM FLOPs) out of the step; gradients are the same bits either way.
+
+Gradient accumulation (the reference's --gradient_accumulation_steps; HF Trainer divides each micro-batch's mean loss by the count and torch adds into .grad):
+forward_backward(..., micro=(i, n)) is micro-batch i of n, accumulate_step(batches) the whole update.  Micro-batch 0 overwrites the gradients, every later one adds
+to them INSIDE the kernels that produce them (csrc/gemm8t.hip's accumulating epilogue, the reducer of csrc/lora.hip, cast_f32_add): the prior 16-bit value joins
+the fp32 sum and the result is rounded once, so the 16-bit gradient buffer takes one rounding per micro-batch where torch's `.grad += T(new)` takes two (T(new), then
+the sum), and no gradient buffer is read and written a second time.  There is no fp32 accumulation buffer.  Buckets are reduce-scattered in the last micro-batch only.
 """
 from __future__ import annotations
 
@@ -381,16 +387,20 @@ class TrainStep:
         self.max_positions = int(max_positions)
         self._pending: List = []
         self._ready: Dict[int, int] = {}
+        self._acc = False                                        # inside a forward_backward call of a micro-batch i > 0: the gradient writers add to self.g
+        self._last_micro = True                                  # ... of the last micro-batch of an update: buckets are reduce-scattered as they complete
+        self._micro_next: Optional[Tuple[int, int]] = None       # the micro-batch an unfinished accumulation waits for (None: optimizer_step may run)
         self.frozen: set = set()
         self.comm_stream = torch.cuda.Stream(device=self.device) if (self.world > 1 and self.device.type == "cuda") else None
 
     # ---- helpers ------------------------------------------------------------------------------------------------------------------------
     def _wgrad(self, dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor) -> None:
-        """out [N, K] = dy[M, N]^T @ x[M, K]   (M is a multiple of the contraction quantum: the packed rows are padded to it)."""
+        """out [N, K] = dy[M, N]^T @ x[M, K]   (M is a multiple of the contraction quantum: the packed rows are padded to it).  In a micro-batch past the first
+        (self._acc) the product is added to what `out` holds, in fp32 before the one rounding."""
         if self.direct_wgrad and ops.wgrad_direct_ok(dy, x, out):
-            ops.gemm_wgrad(dy, x, out)                               # both operands in their forward layout (csrc/gemm8t.hip): no transposed copies
-        else:
-            ops.gemm(ops.transpose_padded(dy, self.kmult), ops.transpose_padded(x, self.kmult), out=out)
+            ops.gemm_wgrad(dy, x, out, accumulate=self._acc)         # both operands in their forward layout (csrc/gemm8t.hip): no transposed copies
+        else:                                                        # residual = out: every GEMM epilogue reads residual[m][n] in the thread that stores out[m][n]
+            ops.gemm(ops.transpose_padded(dy, self.kmult), ops.transpose_padded(x, self.kmult), residual=out if self._acc else None, out=out)
 
     def _dgrad(self, dy: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
         """dy [M, N] @ w [N, K] -> [M, K] (+ residual)."""
@@ -469,7 +479,7 @@ class TrainStep:
         An, Bn = f"model.layers.{l}.{m}.lora_A.weight", f"model.layers.{l}.{m}.lora_B.weight"
         du = self._dgrad(dy, self._lora_sB(l, m))
         if ops.lora_wgrad_ok(dy, u, self.g[Bn]):
-            ops.lora_wgrad(dy, u, self.g[Bn], alpha=self.lora.scaling)
+            ops.lora_wgrad(dy, u, self.g[Bn], alpha=self.lora.scaling, accumulate=self._acc)
         else:                                                # the fp32 verification step, odd shapes: the two-transpose path
             self._wgrad(dy, u * self.lora.scaling, self.g[Bn])
         if self._drop_on and self.lora.dropout > 0.0:
@@ -480,13 +490,13 @@ class TrainStep:
             assert ops.dropout_ok(x), "LoRA dropout: the adapter input must have columns in multiples of 8 and 16-byte aligned rows"
             drop = (*self._drop(), self._drop_stream(l, m))
             if ops.lora_wgrad_ok(x, du, self.g[An], transposed=True):
-                ops.lora_wgrad_dropout(x, du, *drop, out=self.g[An], transposed=True)
+                ops.lora_wgrad_dropout(x, du, *drop, out=self.g[An], transposed=True, accumulate=self._acc)
             else:
                 self._wgrad(du, ops.dropout(x, *drop), self.g[An])
             t = self._dgrad(du, self.p[An])
             return ops.dropout(t, *drop, out=t) if into is None else ops.dropout_add(into, t, *drop)
         if ops.lora_wgrad_ok(x, du, self.g[An], transposed=True):
-            ops.lora_wgrad(x, du, self.g[An], transposed=True)
+            ops.lora_wgrad(x, du, self.g[An], transposed=True, accumulate=self._acc)
         else:
             self._wgrad(du, x, self.g[An])
         return self._dgrad(du, self.p[An], residual=into)
@@ -611,11 +621,14 @@ class TrainStep:
         self.frozen = frozen
 
     def _mark_ready(self, names: Sequence[str]) -> None:
-        """Gradients of `names` are final: reduce-scatter every bucket that just became complete, on the communication stream."""
+        """Gradients of `names` are final for this micro-batch: in the LAST micro-batch of an update, reduce-scatter every bucket that just became complete, on the
+        communication stream (still under that call's backward); earlier micro-batches only accumulate locally in flat_g."""
         P = self.part
         for n in names:
             if n in self.frozen:
                 self.g[n].zero_()
+            if not self._last_micro:
+                continue
             b = P.bucket_of[n]
             self._ready[b] = self._ready.get(b, 0) + 1
             if self._ready[b] == len(P.members[b]):
@@ -718,7 +731,7 @@ class TrainStep:
         dh2 = self._dgrad(du, W[p + "mlp.up_proj.weight"], residual=self._dgrad(dg, W[p + "mlp.gate_proj.weight"], residual=s2))
         dx1, dw = ops.rmsnorm_bwd(st["x1"], W[p + "post_attention_layernorm.weight"], dh2, self.rms_eps, want_dw=not lora, residual=d)     # d joins over the skip connection
         if not lora:
-            ops.cast_f32(dw, G[p + "post_attention_layernorm.weight"])
+            ops.cast_f32(dw, G[p + "post_attention_layernorm.weight"], accumulate=self._acc)
         # attention: x1 = x + o_proj(attn)
         d_attn = self._dgrad(dx1, W[p + "self_attn.o_proj.weight"], residual=side("self_attn.o_proj", dx1, st["attn"]))
         if not lora:
@@ -758,7 +771,7 @@ class TrainStep:
             return dx
         self._wgrad(dqkv, st["h"], self.qkv_g[l])
         dx, dw = ops.rmsnorm_bwd(st["x"], W[p + "input_layernorm.weight"], dh, self.rms_eps, residual=dx1)
-        ops.cast_f32(dw, G[p + "input_layernorm.weight"])
+        ops.cast_f32(dw, G[p + "input_layernorm.weight"], accumulate=self._acc)
         self._mark_ready([p + "mlp.down_proj.weight", p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight", p + "post_attention_layernorm.weight",
                           p + "self_attn.o_proj.weight", p + "self_attn.q_proj.weight", p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight",
                           p + "input_layernorm.weight"])
@@ -788,7 +801,7 @@ class TrainStep:
         for j in reversed(range(n_lin)):
             wn, bn = self.proj_names[2 * j], self.proj_names[2 * j + 1]
             self._wgrad(d, st["ins"][j], G[wn])
-            ops.cast_f32(ops.col_sum(d), G[bn])
+            ops.cast_f32(ops.col_sum(d), G[bn], accumulate=self._acc)
             if j > 0:
                 da = self._dgrad(d, W[wn])
                 d = ops.elementwise(ops.EW_GELU_BWD, st["zs"][j - 1], da)
@@ -796,14 +809,26 @@ class TrainStep:
 
     def forward_backward(self, input_ids: torch.Tensor, labels: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                          image_features: Optional[torch.Tensor] = None, slot_rows: Optional[Sequence[int]] = None, backward: bool = True,
-                         dropout: Optional[bool] = None):
+                         dropout: Optional[bool] = None, micro: Optional[Tuple[int, int]] = None):
         """One micro-batch.  input_ids / labels / attention_mask: [B, L] (ids carry IMAGE_TOKEN_INDEX markers); image_features: output of the
         frozen tower, [n_images, P, mm_hidden] (or a flat [rows, mm_hidden] with slot_rows = rows per image slot).
         Returns (loss fp32 device scalar, number of counted label positions).  Gradients land in self.g (flat_g).
         dropout (LoraConfig.dropout > 0 only): None = `backward`, i.e. a training call draws its masks and advances self.dropout_step, while a forward-only call
         is an evaluation in peft's sense (nn.Dropout is the identity in eval mode): no masks, and the counter, hence the masks of later training calls, stays
-        where it is.  True / False force either (a forward-only look at the training loss; a backward through the unmasked adapters)."""
+        where it is.  True / False force either (a forward-only look at the training loss; a backward through the unmasked adapters).
+        micro = (i, n): this call is micro-batch i of the n that make one optimiser step (gradient accumulation); None = (0, 1).  The loss gradient is scaled by
+        1 / (world * n) (HF Trainer divides each micro-batch's mean loss by n; the returned loss is the micro-batch's own mean).  Micro-batch 0 overwrites every
+        gradient, micro-batches i > 0 add to self.g inside the gradient kernels (one rounding each); buckets are reduce-scattered in micro-batch n - 1 only, and
+        optimizer_step() refuses to run before it."""
         dev, dt = self.device, self.dtype
+        mi, mn = (0, 1) if micro is None else (int(micro[0]), int(micro[1]))
+        if not (mn >= 1 and 0 <= mi < mn):
+            raise ValueError(f"micro = (i, n) needs 0 <= i < n (got {micro})")
+        if backward:
+            if mi > 0 and self._micro_next != (mi, mn):
+                raise RuntimeError(f"micro-batch {mi} of {mn} does not follow the last backward call (expected {self._micro_next or 'a first micro-batch'})")
+            self._acc, self._last_micro = mi > 0, mi == mn - 1
+            self._micro_next = None if mi == mn - 1 else (mi + 1, mn)
         self._drop_on = bool(backward) if dropout is None else bool(dropout)
         if self._drop_on:
             self._drop_step = self.dropout_step                  # one mask set per micro-batch: micro-batches of one accumulation must not share masks
@@ -854,7 +879,7 @@ class TrainStep:
             stash.append({"x": x_in} if (self.checkpoint and l < keep_from) else st)
         hn = ops.rmsnorm(x, self.p["model.norm.weight"], self.rms_eps)
         logits = ops.gemm(hn, self.p["lm_head.weight"])
-        loss, count, dlogits = ops.ce_loss(logits[None], lab_d[None], ignore_index=IGNORE_INDEX, want_grad=backward, grad=1.0 / self.world)
+        loss, count, dlogits = ops.ce_loss(logits[None], lab_d[None], ignore_index=IGNORE_INDEX, want_grad=backward, grad=1.0 / self.world if mn == 1 else 1.0 / (self.world * mn))
         if not backward:
             return loss, count
         # ---- backward (gradients of a data-parallel group are averaged: each rank back-propagates loss / world) ---------------------------
@@ -865,7 +890,7 @@ class TrainStep:
             self._wgrad(dlogits, hn, self.g["lm_head.weight"])
         d, dw = ops.rmsnorm_bwd(x, self.p["model.norm.weight"], dhn, self.rms_eps, want_dw="model.norm.weight" in self.g)
         if "model.norm.weight" in self.g:
-            ops.cast_f32(dw, self.g["model.norm.weight"])
+            ops.cast_f32(dw, self.g["model.norm.weight"], accumulate=self._acc)
         self._mark_ready([n for n in ("lm_head.weight", "model.norm.weight") if n in self.g])
         del logits, dlogits
         for l in reversed(range(self.L)):
@@ -881,17 +906,21 @@ class TrainStep:
         if pst is not None:
             self._projector_backward(pst, dfeats)
         elif self.proj_names:
-            for n in self.proj_names:          # a text-only micro-batch: the projector took no part
-                self.g[n].zero_()
+            if not self._acc:                  # a text-only micro-batch: the projector took no part (an accumulating one adds nothing to what earlier ones left)
+                for n in self.proj_names:
+                    self.g[n].zero_()
             self._mark_ready(self.proj_names)
         if want_dE:
-            ops.cast_f32(dE.view(-1), self.g["model.embed_tokens.weight"].view(-1))
+            ops.cast_f32(dE.view(-1), self.g["model.embed_tokens.weight"].view(-1), accumulate=self._acc)
             self._mark_ready(["model.embed_tokens.weight"])
         return loss, count
 
     # ---- optimiser ------------------------------------------------------------------------------------------------------------------------
     def optimizer_step(self) -> None:
         """Clip by the global norm of the (averaged) gradients, AdamW on this rank's slices, all-gather the updated parameters."""
+        if self._micro_next is not None:
+            raise RuntimeError(f"optimizer_step() in the middle of a gradient accumulation: micro-batch {self._micro_next[0]} of {self._micro_next[1]} has not run "
+                               "(the gradients are partial and, with more than one rank, not reduced)")
         P = self.part
         cur = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
         if self.comm_stream is not None:
@@ -917,6 +946,19 @@ class TrainStep:
     def grad_norm(self) -> float:
         """Global gradient norm of the last step (host read: a sync)."""
         return float(self.gnorm_sq.sqrt().item())
+
+    def accumulate_step(self, batches: Sequence[Sequence]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One optimiser step over len(batches) micro-batches (gradient accumulation): each entry is the argument tuple of forward_backward (input_ids, labels,
+        attention_mask, image_features, slot_rows; trailing ones may be left out).  Returns (mean of the micro-batch losses, total counted positions)."""
+        n = len(batches)
+        if n < 1:
+            raise ValueError("accumulate_step needs at least one micro-batch")
+        losses, counts = [], []
+        for i, args in enumerate(batches):
+            loss, count = self.forward_backward(*args, micro=(i, n))
+            losses.append(loss); counts.append(count)
+        self.optimizer_step()
+        return torch.stack(losses).mean(), torch.stack(counts).sum()
 
     def step(self, input_ids, labels, attention_mask=None, image_features=None, slot_rows=None):
         loss, count = self.forward_backward(input_ids, labels, attention_mask, image_features, slot_rows)

@@ -11,6 +11,7 @@ the HF Trainer, around llava_mi355x/train.py: TrainStep instead.
     save_lora_adapter              llava/train/train.py:987-997        --lora_enable: peft's adapter_config.json + adapter_model.safetensors, non_lora_trainables.bin,
                                                                        config.json — the directory builder.load_pretrained_model(path, base, "...lora...") loads
     train                          llava/train/train.py:805-1000       template by --version, pad = unk, vision setup, dataset + collator (train_data.py), step loop
+    micro_batch_indices            HF Trainer's gradient accumulation   which samples micro-batch i of optimiser step `update` holds on one rank (--gradient_accumulation_steps)
 
 Here a model is a (config, HF-named weight dict) pair — TrainStep owns the parameters in its flat ZeRO-2 buffers, the CLIP tower is the frozen inference tower of
 llava_mi355x/model.py (clip_encoder.py:25: `requires_grad_(False)`), its output enters the step as data.  Freezing (tune_mm_mlp_adapter, freeze_backbone,
@@ -158,6 +159,14 @@ def lr_at(step: int, total_steps: int, base_lr: float, warmup_ratio: float = 0.0
     raise ValueError(f"unsupported lr_scheduler_type {kind!r}")
 
 
+def micro_batch_indices(order, update: int, i: int, rank: int, world: int, B: int, GA: int):
+    """The samples of micro-batch i (0 <= i < GA) of optimiser step `update` of an epoch on rank `rank`: consecutive groups of world x B samples of the epoch's
+    `order`, one group per micro-batch, rank r taking block r of every group — HF Trainer's walk with gradient_accumulation_steps = GA (per_device_train_batch_size x
+    gradient_accumulation_steps x num_gpus samples per optimiser step).  GA = 1 is the walk without accumulation: order[(update * world + rank) * B:][:B]."""
+    first = ((update * GA + i) * world + rank) * B
+    return order[first: first + B]
+
+
 def save_checkpoint(output_dir: str, config, state: Mapping[str, torch.Tensor], model_args) -> str:
     """tune_mm_mlp_adapter: only what that stage trains — `model.mm_projector.*` (+ `model.embed_tokens.weight` with mm_use_im_start_end) — as
     `mm_projector.bin`, the file `pretrain_mm_mlp_adapter` reads back.  Otherwise the whole state dict (HF names) + config.json."""
@@ -217,7 +226,9 @@ def train(model_args, data_args, training_args, *, config, weights: MutableMappi
     from .train import TrainStep
     from .train_data import make_supervised_data_module
     dtype = torch.float16 if training_args.fp16 else (torch.bfloat16 if training_args.bf16 else torch.float32)
-    assert training_args.gradient_accumulation_steps == 1, "gradient accumulation is not wired (TrainStep holds one micro-batch of gradients)"
+    GA = int(training_args.gradient_accumulation_steps)
+    if GA < 1:
+        raise ValueError(f"gradient_accumulation_steps must be at least 1 (got {training_args.gradient_accumulation_steps})")
     # ---- prompt template, padding (train.py:885-907) ----------------------------------------------------------------------------------------------------
     if model_args.version == "v0":
         if tokenizer.pad_token is None:
@@ -282,9 +293,11 @@ def train(model_args, data_args, training_args, *, config, weights: MutableMappi
         import torch.distributed as dist
         world, rank = dist.get_world_size(group), dist.get_rank(group)
     B = int(training_args.per_device_train_batch_size)
-    per_epoch = len(dataset) // (B * world)
+    # optimiser steps per epoch: GA micro-batches of B x world samples each.  Micro-batches left over at the end of an epoch (fewer than GA) are dropped; HF
+    # Trainer carries them over into the next epoch's first update instead (its accumulation counter runs across the epoch boundary)
+    per_epoch = (len(dataset) // (B * world)) // GA
     if per_epoch == 0:
-        raise ValueError(f"{len(dataset)} samples do not fill one batch of {B} x {world}")
+        raise ValueError(f"{len(dataset)} samples do not fill one optimiser step of {B} x {world} x {GA} (batch x ranks x gradient_accumulation_steps)")
     total = training_args.max_steps if training_args.max_steps > 0 else int(math.ceil(training_args.num_train_epochs * per_epoch))
     # ---- the step ----------------------------------------------------------------------------------------------------------------------------------------------
     ts = TrainStep(config, {k: v for k, v in weights.items() if "vision_tower" not in k and not k.startswith("vision.")}, dtype=dtype, device=device,
@@ -299,26 +312,32 @@ def train(model_args, data_args, training_args, *, config, weights: MutableMappi
         # LLaVATrainer._get_train_sampler (llava/train/llava_trainer.py:144-158): batches of similar length, one modality per megabatch
         from .train_data import LengthGroupedSampler
         lengths = [l for part in dataset.datasets for l in part.modality_lengths]
-        sampler = LengthGroupedSampler(B, world_size=world, lengths=lengths, generator=gen, group_by_modality=True)
+        sampler = LengthGroupedSampler(B, world_size=world * GA, lengths=lengths, generator=gen, group_by_modality=True)     # llava_trainer.py:143
     losses, step = [], 0
     while step < total:
-        # the same order on every rank (same seed): rank r takes batch r of every group of `world`
+        # the same order on every rank (same seed): rank r takes batch r of every group of `world`; an optimiser step takes GA such groups.  `step`, the schedule
+        # and max_steps count optimiser steps
         order = list(iter(sampler)) if sampler is not None else torch.randperm(len(dataset), generator=gen).tolist()
         for b in range(per_epoch):
             if step >= total:
                 break
-            first = (b * world + rank) * B
-            batch = collate([dataset[i] for i in order[first: first + B]])
-            feats = None
-            if "images" in batch:
-                pix = batch["images"]
-                if isinstance(pix, (list, tuple)):
-                    raise NotImplementedError("images of different shapes in one batch")
-                feats = vision_tower(pix.to(device=device, dtype=dtype))
             ts.lr = lr_at(step, total, training_args.learning_rate, training_args.warmup_ratio, training_args.lr_scheduler_type)
-            loss, count = ts.step(batch["input_ids"], batch["labels"], batch["attention_mask"], image_features=feats)
+            micro = []
+            for i in range(GA):
+                batch = collate([dataset[j] for j in micro_batch_indices(order, b, i, rank, world, B, GA)])
+                feats = None
+                if "images" in batch:
+                    pix = batch["images"]
+                    if isinstance(pix, (list, tuple)):
+                        raise NotImplementedError("images of different shapes in one batch")
+                    feats = vision_tower(pix.to(device=device, dtype=dtype))
+                micro.append(ts.forward_backward(batch["input_ids"], batch["labels"], batch["attention_mask"], image_features=feats, micro=(i, GA) if GA > 1 else None))
+            ts.optimizer_step()
             step += 1
             if training_args.logging_steps and step % training_args.logging_steps == 0:
+                # a record's loss = the mean of the update's micro-batch losses (what HF Trainer logs), label_positions = their sum
+                loss = micro[0][0] if GA == 1 else torch.stack([l for l, _ in micro]).mean()
+                count = micro[0][1] if GA == 1 else torch.stack([c for _, c in micro]).sum()
                 rec = {"step": step, "loss": float(loss.item()), "learning_rate": ts.lr, "label_positions": int(count)}
                 losses.append(rec["loss"])
                 if log is not None:
