@@ -219,6 +219,22 @@ int lmx_seq_stopped(lmx_seq* s, int32_t* out, void* stream);
  * two bitmaps live in LDS).  Call before lmx_prefill so that the prefill's own pick (token 1) follows the rules too. */
 int lmx_seq_set_logit_rules(lmx_seq* s, float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens, const int64_t* eos_ids, int32_t n_eos,
                             const int64_t* suppress_ids, int32_t n_suppress, const int64_t* prompt_ids_host, int32_t n_prompt, void* stream);
+/* replaces: `output_scores=True` of HF's generate() — the processed fp32 row every step's token was chosen from — and compute_transition_scores on top of it,
+ * for which a caller of this build would otherwise have to re-run the decoder step by step on the host.  Here a score log lives with the sequence: behind every
+ * pick of lmx_prefill / lmx_prefill_batch / lmx_decode / lmx_decode_batch that ADVANCED the sequence, a recorder launch (csrc/sampling.hip; issued only for
+ * sequences with a log: a sequence without one runs exactly the launches it ran before) writes entry idx = (ids generated so far) - 1:
+ *   row p      greedy: the logits row in fp32 after the logits processors (lmx_seq_set_logit_rules) = HF greedy_search's scores;
+ *              sampling: that row / temperature (a true division), -inf for every id outside the top-k / top-p survivor set of the draw = HF sample()'s scores
+ *   logprob    p[token] - logsumexp(p), fp32 (NaN when no entry of p is finite, as torch.log_softmax gives)
+ * cap entries (<= max_position + 8; entries past it are not recorded); want_rows != 0 also keeps the rows ([cap][vocabulary] fp32, the real vocabulary of
+ * lmx_set_vocab_limit), else only the log-probabilities.  cap = 0 detaches.  The engine owns the buffers (allocated here; the call may drain `stream` to grow
+ * them) and clears the log on `stream`.  A pick that did not advance the sequence (device-side stop) records nothing.  lmx_seq_reset, lmx_seq_truncate and the
+ * sequence's return to the pool detach the log: a recycled sequence never records for the next request; lmx_seq_copy does not carry it.  Attach before
+ * lmx_prefill so that the prefill's own pick (entry 0) is recorded. */
+int lmx_seq_set_score_log(lmx_seq* s, int32_t cap, int32_t want_rows, void* stream);
+/* copy out what was recorded (synchronises `stream`): *n_out = min(entries recorded, max_n); logprob_host[0, *n_out); rows_dev_or_null (device,
+ * [>= *n_out][vocabulary] fp32, only for a log attached with want_rows): the rows, device to device. */
+int lmx_seq_read_scores(lmx_seq* s, float* logprob_host, int32_t max_n, int32_t* n_out, float* rows_dev_or_null, void* stream);
 
 /* ---- decode batch: continuous batching --------------------------------------------------------------
  * new in this build: the reference serves up to --limit-model-concurrency requests as independent generate() threads with no
@@ -324,6 +340,15 @@ int lmx_op_pick_rules(int32_t dtype, const void* logits_dev, int32_t V, int32_t 
                       float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens, const int64_t* eos_ids, int32_t n_eos,
                       const int64_t* suppress_ids, int32_t n_suppress, float temperature, float top_p, int32_t top_k, uint64_t seed,
                       const uint32_t* u32_override_host, int64_t* out_tok_dev, float* processed_row_dev, uint8_t* keep_out_dev, void* stream);
+/* The score recorder's arithmetic on a caller-supplied row (stands to lmx_seq_set_score_log as lmx_op_pick_rules stands to the ruled pick): row, history and rules
+ * as for lmx_op_pick_rules; temperature <= 0: the greedy row, else the sampled one (keep_scratch_dev: [V] bytes, required; u32_override_host as in lmx_op_sample).
+ * row_out_dev ([V] fp32, may be NULL) = the processed row; lse_logprob_dev[0] = its log-sum-exp, [1] = row[token] - lse; token < 0 (sampled rows only): the id
+ * re-drawn under the uniform number; redraw_tok_dev (may be NULL): that id (-1 for a greedy row).  Only ids [0, V) of the row are read; the row stays raw. */
+int lmx_op_score_row(int32_t dtype, const void* logits_dev, int32_t V, int32_t ld, const int64_t* history_dev, int32_t n_hist, int32_t n_out,
+                     float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens, const int64_t* eos_ids, int32_t n_eos,
+                     const int64_t* suppress_ids, int32_t n_suppress, float temperature, float top_p, int32_t top_k, uint64_t seed,
+                     const uint32_t* u32_override_host, int64_t token, float* row_out_dev, float* lse_logprob_dev, int64_t* redraw_tok_dev,
+                     uint8_t* keep_scratch_dev, void* stream);
 int lmx_op_argmax(int32_t dtype, const void* logits, int32_t V, int64_t* out_tok_dev, void* stream);
 int lmx_op_im2col(int32_t dtype, const void* pixels, void* out, int32_t N, int32_t S, int32_t patch, int32_t kpad, void* stream);
 

@@ -200,6 +200,7 @@ int lmx_seq_create(lmx_model* m, lmx_seq** out) {
         s->impl.len = 0;
         s->impl.samp = SampleParams{};
         s->impl.clear_logit_rules();
+        s->impl.clear_score_log();
         s->impl.uid = next_seq_uid();
         zero_fill(s->impl.state.p, 16);
         zero_fill(s->impl.stopbuf.p, sizeof(StopSpec));
@@ -216,6 +217,7 @@ int lmx_seq_destroy(lmx_seq* s) {
     Model* m = s->impl.m;
     if (m) m->live_seqs.fetch_sub(1, std::memory_order_relaxed);
     s->impl.clear_logit_rules();          // a pooled sequence carries no request's logits processors
+    s->impl.clear_score_log();            // ... and records no scores for the next request
     bool pooled = false;
     bool idle_known = true;
     if (m && s->impl.used) {
@@ -229,6 +231,9 @@ int lmx_seq_destroy(lmx_seq* s) {
     // pool with the sequence: above the size of a ~2.5k-row prefill it is freed here (hipFree waits for the device), so pooled sequences stay KV-sized.
     constexpr size_t kPwsKeepMax = (size_t)192 << 20;
     if (m && idle_known && s->impl.pws.bytes > kPwsKeepMax) s->impl.pws.release();
+    // the full-row score buffer (entries x vocabulary x 4 bytes: 128 MB for 1024 entries at 32000 ids) likewise stays with a pooled sequence only while small
+    constexpr size_t kScoreRowsKeepMax = (size_t)64 << 20;
+    if (m && idle_known && s->impl.score_rows.bytes > kScoreRowsKeepMax) s->impl.score_rows.release();
     if (m && idle_known) {
         std::lock_guard<std::mutex> lk(m->pool_mu);
         const size_t bytes = s->impl.kc.bytes + s->impl.vt.bytes + s->impl.dws.bytes + s->impl.pws.bytes;
@@ -314,6 +319,48 @@ int lmx_op_pick_rules(int32_t dtype, const void* logits_dev, int32_t V, int32_t 
                       u32_override_host, out_tok_dev, processed_row_dev, keep_out_dev, S(stream));
     LMX_API_END
 }
+int lmx_seq_set_score_log(lmx_seq* s, int32_t cap, int32_t want_rows, void* stream) {
+    LMX_API_BEGIN
+    LMX_REQUIRE(s, "null sequence");
+    LMX_REQUIRE(cap >= 0, "set_score_log: negative capacity (0 detaches the log)");
+    s->impl.set_score_log(cap, want_rows != 0, S(stream));
+    LMX_API_END
+}
+int lmx_seq_read_scores(lmx_seq* s, float* logprob_host, int32_t max_n, int32_t* n_out, float* rows_dev_or_null, void* stream) {
+    LMX_API_BEGIN
+    LMX_REQUIRE(s && logprob_host && n_out && max_n >= 0, "null argument");
+    LMX_REQUIRE(s->impl.score_cap > 0, "read_scores: the sequence has no score log (lmx_seq_set_score_log)");
+    LMX_REQUIRE(!rows_dev_or_null || s->impl.score_rows_on, "read_scores: the score log was attached without rows");
+    const ScoreRef sc = s->impl.score_ref();
+    int n = 0;
+    LMX_CHECK_HIP(hipMemcpyAsync(&n, sc.n_scored, sizeof(int), hipMemcpyDeviceToHost, S(stream)));
+    LMX_CHECK_HIP(hipStreamSynchronize(S(stream)));
+    if (n > sc.cap) n = sc.cap;
+    if (n > max_n) n = max_n;
+    if (n > 0) {
+        if (rows_dev_or_null)
+            LMX_CHECK_HIP(hipMemcpyAsync(rows_dev_or_null, sc.rows, (size_t)n * s->impl.m->Vr * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+        LMX_CHECK_HIP(hipMemcpyAsync(logprob_host, sc.logprob, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, S(stream)));
+        LMX_CHECK_HIP(hipStreamSynchronize(S(stream)));
+    }
+    *n_out = n;
+    LMX_API_END
+}
+int lmx_op_score_row(int32_t dtype, const void* logits_dev, int32_t V, int32_t ld, const int64_t* history_dev, int32_t n_hist, int32_t n_out,
+                     float repetition_penalty, int32_t no_repeat_ngram, int32_t min_new_tokens, const int64_t* eos_ids, int32_t n_eos,
+                     const int64_t* suppress_ids, int32_t n_suppress, float temperature, float top_p, int32_t top_k, uint64_t seed,
+                     const uint32_t* u32_override_host, int64_t token, float* row_out_dev, float* lse_logprob_dev, int64_t* redraw_tok_dev,
+                     uint8_t* keep_scratch_dev, void* stream) {
+    LMX_API_BEGIN
+    LMX_REQUIRE(logits_dev && lse_logprob_dev && V > 0 && ld >= V, "score_row: null argument or row pitch below V");
+    LMX_REQUIRE(n_hist == 0 || history_dev, "score_row: null history");
+    LMX_REQUIRE(n_out >= 0 && n_out <= n_hist, "score_row: n_out counts the generated ids at the end of the history");
+    LogitRules r = make_rules(repetition_penalty, no_repeat_ngram, min_new_tokens, eos_ids, n_eos, suppress_ids, n_suppress, n_hist);
+    r.prompt = history_dev;
+    launch_score_row(dtype, logits_dev, V, r, n_out, SampleParams{temperature > 0.f ? temperature : 0.f, top_p, top_k, (uint32_t)seed, (uint32_t)(seed >> 32)},
+                     u32_override_host, token, keep_scratch_dev, row_out_dev, lse_logprob_dev, redraw_tok_dev, S(stream));
+    LMX_API_END
+}
 int lmx_op_sample(int32_t dtype, const void* logits_dev, int32_t V, float temperature, float top_p, int32_t top_k, uint64_t seed,
                   const int32_t* offset_dev, const uint32_t* u32_override_host, int64_t* out_tok_dev, uint8_t* keep_out_dev, void* stream) {
     LMX_API_BEGIN
@@ -328,6 +375,7 @@ int lmx_seq_reset(lmx_seq* s) {
     zero_fill(s->impl.state.p, 16);       // caller guarantees no work on this sequence is in flight
     zero_fill(&s->impl.d_stop->done, sizeof(int));      // a sequence that stopped by its id rule is live again (the rule itself stays until the next set_stop)
     s->impl.clear_logit_rules();                        // the logits processors belong to the request that set them
+    s->impl.clear_score_log();                          // and so does the score log
     LMX_API_END
 }
 int lmx_seq_length(const lmx_seq* s) { return s ? s->impl.len : -1; }
@@ -828,6 +876,7 @@ int lmx_seq_truncate(lmx_seq* s, int32_t n_rows, void* stream) {
     s->impl.len = n_rows;
     s->impl.samp = SampleParams{};
     s->impl.clear_logit_rules();
+    s->impl.clear_score_log();
     s->impl.uid = next_seq_uid();
     s->impl.last_stream = S(stream); s->impl.used = true;
     launch_set_state(s->impl.d_len, n_rows, s->impl.d_tok, 0, 1, s->impl.d_nout, 0, S(stream));

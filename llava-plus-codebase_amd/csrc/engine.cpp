@@ -568,6 +568,24 @@ void Seq::set_logit_rules(const LogitRules& r, const int64_t* prompt_host, hipSt
     uid = next_seq_uid();          // a decode batch holding this sequence rebuilds its table entry
 }
 
+// Attach (cap entries; want_rows: the full fp32 rows too) or, with cap = 0, detach the score log.  Growing a buffer frees the old one, so the stream is drained
+// first; the state words are cleared on `st`, ordered with the sequence's work there.
+void Seq::set_score_log(int cap, bool want_rows, hipStream_t st) {
+    if (cap <= 0) { clear_score_log(); return; }
+    LMX_REQUIRE(cap <= log_cap, "set_score_log: more entries than the sequence's token log holds (max_position + 8)");
+    const size_t state_off = ((size_t)cap * sizeof(float) + 15) / 16 * 16;
+    const size_t need = state_off + 16 + (size_t)m->Vr, need_rows = want_rows ? (size_t)cap * m->Vr * sizeof(float) : 0;
+    if (need > scorebuf.bytes || need_rows > score_rows.bytes) {
+        LMX_CHECK_HIP(hipStreamSynchronize(st));
+        scorebuf.ensure(need);
+        if (need_rows) score_rows.ensure(need_rows);
+    }
+    score_cap = cap; score_rows_on = want_rows;
+    LMX_CHECK_HIP(hipMemsetAsync(scorebuf.p, 0, state_off + 16, st));      // logprob = 0, n_scored = 0
+    last_stream = st; used = true;
+    uid = next_seq_uid();          // a decode batch holding this sequence rebuilds its table entry
+}
+
 Seq::~Seq() {
     if (h_prompt) (void)hipHostFree(h_prompt);
     if (ev_prompt) (void)hipEventDestroy(ev_prompt);
@@ -707,6 +725,16 @@ void Model::prefill_head(Seq* s, const void* h_row, void* dst, bool pick, hipStr
     else if (s->samp.temperature > 0.f) launch_sample(dt, dst, Vr, s->samp, s->d_nout, s->d_tok, nullptr, nullptr, st);
     else launch_argmax(dt, dst, Vr, s->d_tok, st);
     launch_log_token(s->d_tok, s->d_log, s->d_nout, s->log_cap, s->d_stop, st);
+    record_scores(s, dst, st);
+}
+
+// the score recorder behind a pick of one sequence (sampling.hip); nothing is launched for a sequence without a score log
+void Model::record_scores(Seq* s, const void* logits, hipStream_t st) {
+    if (s->score_cap <= 0) return;
+    LMX_PROF("decode.score");
+    const SeqStateRef r = s->state_ref();
+    const ScoreRef sc = s->score_ref();
+    launch_score_record(cfg.dtype, logits, Vr, V, nullptr, &r, nullptr, &sc, 1, s->rules_on, st);
 }
 
 // One sequence in pieces of `chunk` rows: each piece is one segment, which may fuse RoPE into the q|k|v GEMM and take the two-half pipeline
@@ -851,6 +879,7 @@ void Model::decode_step_launch(Seq* s, hipStream_t st, int64_t* id_out) {
         const SeqStateRef r = s->state_ref();
         launch_argmax_advance_batch(dt, s->d_logits, Vr, V, nullptr, &r, 1, id_out, embed, s->d_h, H, st, s->rules_on);      // id_out: the picked id, or -1 once the stop rule has fired
     }
+    record_scores(s, s->d_logits, st);      // the next step's lm_head overwrites d_logits only behind it on the stream
 }
 
 void Model::seq_copy(Seq* dst, const Seq* src, hipStream_t st) {
@@ -924,6 +953,8 @@ Batch::Batch(Model* mm, int capacity) : m(mm), cap(capacity) {
     h = W + o_h; x = W + o_x; qkv = W + o_qkv; attn = W + o_attn; act = W + o_act; logits = W + o_log;
     const size_t attn_bytes = sizeof(DecodeFusedSeq) * (size_t)m->L * cap, state_bytes = sizeof(SeqStateRef) * (size_t)cap;
     tab.ensure(attn_bytes + state_bytes, true);
+    score_tab.ensure(sizeof(ScoreRef) * (size_t)cap, true);
+    host_score_tab.resize((size_t)cap);
     if (m->cfg.dtype != kF32) {                     // K-sliced linears of a decode batch: o_proj / down_proj (N = H) and q|k|v
         const int nmax = std::max(m->H, m->qkv_n);
         sk_scratch.ensure(skinny_scratch_bytes(nmax)); sk_cnt.ensure((size_t)(nmax / 64 + 1) * sizeof(int), true);
@@ -947,10 +978,12 @@ void Batch::bind(Seq* const* seqs, int n, hipStream_t st) {
             at[(size_t)l * cap + i] = DecodeFusedSeq{s->kc.as<char>() + (size_t)l * s->layer_stride, s->vt.as<char>() + (size_t)l * s->layer_stride,
                                                      s->d_len, s->d_aws, s->d_cnt};
         stt[i] = s->state_ref();
+        host_score_tab[(size_t)i] = s->score_ref();
     }
     // the previous step's kernels may still be reading the old tables on this stream, and the host image is reused
     LMX_CHECK_HIP(hipStreamSynchronize(st));
     LMX_CHECK_HIP(hipMemcpyAsync(tab.p, host_tab.data(), host_tab.size(), hipMemcpyHostToDevice, st));
+    LMX_CHECK_HIP(hipMemcpyAsync(score_tab.p, host_score_tab.data(), sizeof(ScoreRef) * (size_t)n, hipMemcpyHostToDevice, st));
     LMX_CHECK_HIP(hipStreamSynchronize(st));
     members.resize((size_t)n);
     for (int i = 0; i < n; ++i) members[(size_t)i] = seqs[i]->uid;
@@ -974,7 +1007,8 @@ void Model::decode_batch(Batch* b, Seq* const* seqs, int n, const int64_t* token
     if (n > 1) ensure_batch_weights(st);
     b->bind(seqs, n, st);
     bool any_rules = false;        // per launch: the rules-carrying pick only when some member has logits processors
-    for (int i = 0; i < n; ++i) any_rules = any_rules || seqs[i]->rules_on;
+    bool any_scores = false;       // per launch: the score recorder only when some member has a score log
+    for (int i = 0; i < n; ++i) { any_rules = any_rules || seqs[i]->rules_on; any_scores = any_scores || seqs[i]->score_cap > 0; }
     if (n_steps > b->ids_steps) { LMX_CHECK_HIP(hipStreamSynchronize(st)); b->ids.ensure((size_t)n_steps * b->cap * 8); b->ids_steps = n_steps; }
     int64_t* d_ids = b->ids.as<int64_t>();
     if (tokens)
@@ -1032,6 +1066,7 @@ void Model::decode_batch(Batch* b, Seq* const* seqs, int n, const int64_t* token
         gather_logits(b->logits, n, st);
         // pick + advance + the picked tokens' embedding rows -> b->h (input of the next step), one launch
         { LMX_PROF("decode_batch.argmax"); launch_argmax_advance_batch(dt, b->logits, Vr, V, b->d_state_tab, nullptr, n, d_ids + (size_t)step * b->cap, embed, b->h, H, st, any_rules); }
+        if (any_scores) { LMX_PROF("decode_batch.score"); launch_score_record(dt, b->logits, Vr, V, b->d_state_tab, nullptr, b->score_tab.as<ScoreRef>(), nullptr, n, any_rules, st); }
         for (int i = 0; i < n; ++i) seqs[i]->len += 1;
     }
     }

@@ -155,6 +155,7 @@ struct Model {
     void prefill_piece(const PrefillWs& ws, const std::vector<PrefillSeg>& seg, int rows, const PieceOpts& o, hipStream_t st);
     // lm_head (+ final norm) of one hidden row into dst [V]; pick: s's next token (sample / argmax) and its log entry
     void prefill_head(Seq* s, const void* h_row, void* dst, bool pick, hipStream_t st);
+    void record_scores(Seq* s, const void* logits, hipStream_t st);      // the score recorder behind a pick on `logits`, if s has a score log
     void decode_step_launch(Seq* s, hipStream_t st, int64_t* id_out = nullptr);      // id_out (device): this step's picked id, -1 after a device-side stop
     void seq_copy(Seq* dst, const Seq* src, hipStream_t st);      // dst := src's context (KV of the first src->len positions, length): beam reordering
     void decode_batch(struct Batch* b, Seq* const* seqs, int n, const int64_t* tokens, int n_steps, void* logits, bool greedy, int64_t* ids_out_host, hipStream_t st,
@@ -205,6 +206,19 @@ struct Seq {
     void set_logit_rules(const LogitRules& r, const int64_t* prompt_host, hipStream_t st);      // r.prompt is ignored: the ids come from prompt_host
     void clear_logit_rules() { if (rules_on) { rules_on = false; rules = LogitRules{}; uid = next_seq_uid(); } }
     SeqStateRef state_ref() const { return SeqStateRef{d_len, d_nout, d_tok, d_log, log_cap, 0, samp, d_stop, d_rules()}; }
+    // score log (lmx_seq_set_score_log; kernels.h: ScoreRef): score_cap > 0 = attached, only then does a recorder launch follow this sequence's picks.
+    // The buffers are allocated by the setter and stay with the sequence when the log is marked off (reset, truncate, return to the pool: the next
+    // request never records into them unasked); scorebuf = logprob[cap] floats | n_scored | keep[V] bytes, score_rows = rows[cap][Vr] floats (want_rows only)
+    DevBuf scorebuf, score_rows; int score_cap = 0; bool score_rows_on = false;
+    size_t score_state_off() const { return ((size_t)score_cap * sizeof(float) + 15) / 16 * 16; }
+    ScoreRef score_ref() const {
+        if (score_cap <= 0) return ScoreRef{};
+        char* b = scorebuf.as<char>();
+        return ScoreRef{reinterpret_cast<float*>(b), score_rows_on ? score_rows.as<float>() : nullptr, reinterpret_cast<uint8_t*>(b + score_state_off() + 16), score_cap, 0,
+                        reinterpret_cast<int*>(b + score_state_off())};
+    }
+    void set_score_log(int cap, bool want_rows, hipStream_t st);      // cap 0 detaches
+    void clear_score_log() { if (score_cap > 0) { score_cap = 0; score_rows_on = false; uid = next_seq_uid(); } }
     DevBuf pws;                        // prefill workspace
     DevBuf skw;                        // split-K partial tiles of the ping-pong GEMM (o_proj, down_proj of a prefill)
     DevBuf dws;                        // decode workspace
@@ -234,6 +248,7 @@ struct Batch {
     DecodeFusedSeq* d_attn_tab = nullptr; SeqStateRef* d_state_tab = nullptr;
     std::vector<uint64_t> members;     // Seq::uid of what the device tables currently describe
     std::vector<char> host_tab;
+    DevBuf score_tab; std::vector<ScoreRef> host_score_tab;      // device: ScoreRef[cap], rebuilt with the tables above (members without a score log: all zero)
     DevBuf ids; int ids_steps = 0;     // [ids_steps][cap] int64: greedy picks of the chained steps of the last call
     DevBuf sk_scratch, sk_cnt;         // skinny kernel's K slices across workgroups (narrow layers): fp32 partial tiles of one launch, one ticket per 64-row tile (zeroed once)
     Batch(Model* mm, int capacity);

@@ -284,6 +284,24 @@ void launch_set_logit_rules(LogitRules* dst, const LogitRules& v, hipStream_t st
 void launch_pick_rules(int dtype, const void* logits, int V, const LogitRules& rules, const int64_t* log, int log_cap, const int* n_out_ptr, int n_out,
                        const SampleParams& p, const uint32_t* u32_override, int64_t* out_tok, float* processed, uint8_t* keep_out, hipStream_t st);
 
+// ---- score log of a sequence (lmx_seq_set_score_log; sampling.hip: the recorder) ----------------------------------------------------------------------
+// What HF's generate(output_scores=True) keeps per step, written by a launch of its own behind the pick: entry idx = (generated ids so far) - 1 gets
+// logprob[idx] = log_softmax(p)[tok] and, when rows != null, rows[idx][0, V) = p, the fp32 row the pick chose from (after the logits processors; for a sampling
+// sequence also after temperature / top-k / top-p, non-survivors -inf).  keep: [V] bytes of scratch for the re-run sampler's survivor set.  n_scored: the
+// value of n_out the log is complete for — a pick that did not advance the sequence (stop rule) records nothing.  logprob == null or cap <= 0: no log.
+// The state travels in a table of its own: SeqStateRef and the picks do not know about it.
+struct ScoreRef { float* logprob; float* rows; uint8_t* keep; int cap; int pad; int* n_scored; };
+// n members (one workgroup each) of the step whose pick has just run on `logits` ([n][ld], V ids read per row): state and score log from the device tables
+// tab / stab, or one by-value pair (single / ssingle, host pointers; n must be 1).  rules: some member carries LogitRules (as for the pick)
+void launch_score_record(int dtype, const void* logits, int V, int ld, const SeqStateRef* tab, const SeqStateRef* single, const ScoreRef* stab, const ScoreRef* ssingle,
+                         int n, bool rules, hipStream_t st);
+// The recorder's arithmetic on a caller-supplied row: history = rules.prompt[0, n_prompt) (device), n_out feeds the min-new-tokens rule and the Philox offset;
+// p.temperature <= 0: greedy row, else the sampled one (u32_override: host pointer, as for launch_sample; keep: [V] device scratch, required).
+// row_out ([V] fp32, may be null) = p; lse_lp[0] = log-sum-exp of p, lse_lp[1] = p[tok] - lse; tok < 0 (sampled only) = the id re-drawn under u;
+// redraw_out (may be null): that id (-1 for a greedy row)
+void launch_score_row(int dtype, const void* logits, int V, const LogitRules& rules, int n_out, const SampleParams& p, const uint32_t* u32_override, int64_t tok,
+                      uint8_t* keep, float* row_out, float* lse_lp, int64_t* redraw_out, hipStream_t st);
+
 // ---- one-shot peer-to-peer all-reduce for decode-sized messages (p2p.hip) ---------------------------------------------
 constexpr int P2P_MAX_ROWS = 32;     // rows ([H] each) per launch = largest decode batch that goes through the skinny path
 constexpr int P2P_MAX_WORLD = 8;

@@ -150,7 +150,9 @@ struct SampleScratch {
 };
 
 // Returns the sampled token id (valid in every thread).  keep_out (debug, may be null): 1 for every surviving token id.
-template <typename T, bool RULES = false>
+// USER only names the instantiation: the score recorder takes instances of its own (USER = 1), so the picks' instances keep the callers — and with them the
+// inlining and the machine code — they had before the recorder existed.
+template <typename T, bool RULES = false, int USER = 0>
 __device__ int64_t sample_row(const T* __restrict__ logits, int V, float temperature, float top_p, int top_k, uint32_t u32,
                               SampleScratch& sh, uint8_t* __restrict__ keep_out, RuleView<RULES> rv = {}) {
     const int tid = threadIdx.x;
@@ -701,6 +703,137 @@ void launch_beam_topk(int dtype, const void* logits, int ld, int V, int rows, co
     LMX_REQUIRE(rows >= 1 && K >= 1 && K <= 64 && V >= 1, "beam_topk: bad arguments");
     dispatch_dtype(dtype, "beam_topk", [&](auto t) {
         hipLaunchKernelGGL(beam_topk_kernel<LMX_T(t)>, dim3(rows), dim3(1024), 0, st, (const LMX_T(t)*)logits, ld, V, beam_scores, K, out_scores, out_ids);
+    });
+    LMX_CHECK_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Score recorder (generate(output_scores=True) / lmx_seq_set_score_log): what HF's generate() stores in `scores` for the step whose token a pick has just
+// logged, and that token's log-probability — a launch of its own BEHIND the pick, issued only for sequences that asked, so a request that did not ask runs the
+// launches it always ran.  One 1024-thread workgroup per sequence recomputes the row the pick saw from the raw logits (which stay raw):
+//   greedy : p_i = adjust(float(l_i))                                       (greedy_search: the processors' output)
+//   sampled: p_i = keep_i ? adjust(float(l_i)) / temperature : -inf         (sample: processors, TemperatureLogitsWarper — a true division —, TopK, TopP)
+// with keep = the survivor set of the streaming sampler re-run under the same uniform number (so the re-drawn id is the logged one), then
+//   lse = max + log(sum exp(p_i - max)), logprob = p_tok - lse              fp32; per-thread strided sums, wave shuffle, 16 wave sums in index order: the
+// reduction order is fixed, two runs give the same bits.  A row without a finite entry records NaN (torch.log_softmax's answer), decided by a branch and not by
+// what -inf - -inf happens to compile to.  Only ids [0, V) of the row are read; the pitch's padding behind them never is.
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T, bool RULES>
+__device__ __forceinline__ void score_row_body(const T* __restrict__ logits, int V, const RuleView<RULES>& rv, const SampleParams& sp, uint32_t u, int64_t tok,
+                                               bool tok_is_redraw, SampleShared& sh, float* red16, uint8_t* keep, float* __restrict__ row_out,
+                                               float* __restrict__ lse_out, float* __restrict__ lp_out, int64_t* __restrict__ redraw_out) {
+    const int tid = threadIdx.x;
+    const bool sampled = sp.temperature > 0.f;
+    if (sampled) {
+        int64_t redraw;
+        [[clang::always_inline]] redraw = sample_row<T, RULES, 1>(logits, V, sp.temperature, sp.top_p, sp.top_k, u, sh.generic, keep, rv);
+        if (tok_is_redraw) tok = redraw;
+        if (redraw_out && tid == 0) *redraw_out = redraw;
+        __syncthreads();                                    // keep[] was written chunk-wise, it is read id-strided below
+    }
+    const float temp = sp.temperature;
+    auto p_of = [&](int i) {
+        const float v = adjust(rv, i, to_f32(logits[i]));
+        if (!sampled) return v;
+        return keep[i] ? __fdiv_rn(v, temp) : -INFINITY;
+    };
+    float mx = -INFINITY;
+    for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, p_of(i));
+    mx = block_max_1024(mx, red16);
+    const bool any_finite = mx > -INFINITY && mx < INFINITY;
+    float sum = 0.f;
+    for (int i = tid; i < V; i += 1024) {
+        const float p = p_of(i);
+        if (row_out) row_out[i] = p;
+        if (any_finite && p > -INFINITY) sum += expf(p - mx);
+    }
+    sum = wave_sum(sum);
+    if ((tid & 63) == 0) red16[tid >> 6] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        float tot = 0.f;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) tot += red16[w];
+        const float nan = __uint_as_float(0x7fc00000u);
+        const float lse = any_finite ? mx + logf(tot) : nan;
+        const float pt = (tok >= 0 && tok < (int64_t)V) ? p_of((int)tok) : nan;
+        if (lse_out) *lse_out = lse;
+        *lp_out = any_finite ? pt - lse : nan;
+    }
+}
+
+// the recorder behind a pick: state from the pick's own table (`tab`, decode batch) or by value (`single`), the score log likewise
+template <typename T, bool RULES>
+__global__ __launch_bounds__(1024) void score_record_kernel(const T* __restrict__ logits_all, int V, int ld, const SeqStateRef* __restrict__ tab, SeqStateRef single,
+                                                            const ScoreRef* __restrict__ stab, ScoreRef ssingle) {
+    __shared__ SampleShared sh;
+    __shared__ float red16[16];
+    const ScoreRef sc = stab ? stab[blockIdx.x] : ssingle;
+    if (!sc.logprob || sc.cap <= 0) return;                   // this member has no log (workgroup-uniform, like everything below)
+    const SeqStateRef r = tab ? tab[blockIdx.x] : single;
+    const int n = *r.n_out;
+    // the pick did not advance (the stop rule had fired earlier), or the entry is beyond the log / the token log
+    if (*sc.n_scored >= n || n - 1 >= sc.cap || n - 1 >= r.log_cap || !r.log) return;
+    const int idx = n - 1;
+    const int64_t tok = r.log[idx];
+    __syncthreads();                                          // everyone has read n_scored before thread 0 moves it
+    const T* logits = logits_all + (size_t)blockIdx.x * ld;
+    RuleView<RULES> rv{};
+    if constexpr (RULES) {
+        rv.on = false;
+        if (r.rules) {
+            const LogitRules lr = *r.rules;
+            if (!logit_rules_neutral(lr)) rv = build_rule_bitmaps<1024>(lr, r.log, idx, idx, V);      // the history as the pick saw it: without tok
+        }
+    }
+    const uint32_t u = philox_u32(r.sample.seed_lo, r.sample.seed_hi, (uint32_t)idx);
+    score_row_body<T, RULES>(logits, V, rv, r.sample, u, tok, false, sh, red16, sc.keep, sc.rows ? sc.rows + (size_t)idx * V : nullptr, nullptr, sc.logprob + idx,
+                             nullptr);
+    if (threadIdx.x == 0) *sc.n_scored = n;
+}
+
+void launch_score_record(int dtype, const void* logits, int V, int ld, const SeqStateRef* tab, const SeqStateRef* single, const ScoreRef* stab, const ScoreRef* ssingle,
+                         int n, bool rules, hipStream_t st) {
+    LMX_REQUIRE((tab != nullptr) != (single != nullptr) && (stab != nullptr) == (tab != nullptr) && (ssingle != nullptr) == (single != nullptr) && (tab || n == 1),
+                "score_record: give device tables or one by-value state and score log");
+    LMX_REQUIRE(V > 0 && ld >= V && (!rules || V <= RULES_MAX_V), "score_record: bad row geometry, or the vocabulary is too large for the logits-processor bitmaps");
+    const SeqStateRef one = single ? *single : SeqStateRef{};
+    const ScoreRef sone = ssingle ? *ssingle : ScoreRef{};
+    dispatch_dtype(dtype, "score_record", [&](auto t) {
+        using T = LMX_T(t);
+        const auto kern = rules ? score_record_kernel<T, true> : score_record_kernel<T, false>;
+        hipLaunchKernelGGL(kern, dim3(n), dim3(1024), rules ? rule_bits_bytes(V) : 0, st, (const T*)logits, V, ld, tab, one, stab, sone);
+    });
+    LMX_CHECK_HIP(hipGetLastError());
+}
+
+// the same body on a caller-supplied row, history and rules (kernels.h: launch_score_row)
+template <typename T, bool RULES>
+__global__ __launch_bounds__(1024) void score_row_kernel(const T* __restrict__ logits, int V, LogitRules lr, const int64_t* __restrict__ log, int n_log, int n_out, SampleParams p, uint32_t u32_override,
+                                                         int use_override, int64_t tok, uint8_t* keep, float* __restrict__ row_out, float* __restrict__ lse_lp,
+                                                         int64_t* __restrict__ redraw_out) {
+    __shared__ SampleShared sh;
+    __shared__ float red16[16];
+    RuleView<RULES> rv{};
+    if constexpr (RULES) rv = build_rule_bitmaps<1024>(lr, log, n_log, n_out, V);
+    const uint32_t u = use_override ? u32_override : philox_u32(p.seed_lo, p.seed_hi, (uint32_t)n_out);
+    if (redraw_out && p.temperature <= 0.f && threadIdx.x == 0) *redraw_out = -1;
+    score_row_body<T, RULES>(logits, V, rv, p, u, tok, tok < 0, sh, red16, keep, row_out, lse_lp, lse_lp + 1, redraw_out);
+}
+
+void launch_score_row(int dtype, const void* logits, int V, const LogitRules& rules, int n_out, const SampleParams& p, const uint32_t* u32_override, int64_t tok,
+                      uint8_t* keep, float* row_out, float* lse_lp, int64_t* redraw_out, hipStream_t st) {
+    LMX_REQUIRE(V > 0 && V <= RULES_MAX_V && lse_lp, "score_row: null output, or the vocabulary is too large for the logits-processor bitmaps");
+    LMX_REQUIRE(p.temperature <= 0.f || (p.top_p > 0.f && keep), "score_row: a sampled row needs top_p > 0 and the [V] survivor scratch");
+    LMX_REQUIRE(tok < (int64_t)V && (tok >= 0 || p.temperature > 0.f), "score_row: token outside [0, V) (a negative one = the re-drawn id, sampled rows only)");
+    LMX_REQUIRE(rules.n_eos >= 0 && rules.n_eos <= RULES_MAX_EOS && rules.n_suppress >= 0 && rules.n_suppress <= RULES_MAX_SUPPRESS && rules.n_prompt >= 0,
+                "score_row: at most 4 end-of-sequence ids and 16 suppressed ids");
+    const bool ruled = !logit_rules_neutral(rules);
+    dispatch_dtype(dtype, "score_row", [&](auto t) {
+        using T = LMX_T(t);
+        const auto kern = ruled ? score_row_kernel<T, true> : score_row_kernel<T, false>;
+        hipLaunchKernelGGL(kern, dim3(1), dim3(1024), ruled ? rule_bits_bytes(V) : 0, st, (const T*)logits, V, rules, (const int64_t*)nullptr, 0, n_out, p, u32_override ? *u32_override : 0u,
+                           u32_override ? 1 : 0, tok, keep, row_out, lse_lp, redraw_out);
     });
     LMX_CHECK_HIP(hipGetLastError());
 }

@@ -87,6 +87,8 @@ _SIGS = {
     "lmx_seq_set_stop": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "lmx_seq_stopped": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "lmx_seq_set_logit_rules": (c_int32, [c_void_p, c_float, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "lmx_seq_set_score_log": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
+    "lmx_seq_read_scores": (c_int32, [c_void_p, c_void_p, c_int32, _i32p, c_void_p, c_void_p]),
     "lmx_seq_reset": (c_int32, [c_void_p]),
     "lmx_seq_length": (c_int32, [c_void_p]),
     "lmx_prefill": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
@@ -125,6 +127,8 @@ _SIGS = {
     "lmx_op_sample": (c_int32, [c_int32, c_void_p, c_int32, c_float, c_float, c_int32, ctypes.c_uint64, c_void_p, POINTER(ctypes.c_uint32), c_void_p, c_void_p, c_void_p]),
     "lmx_op_pick_rules": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                     c_float, c_float, c_int32, ctypes.c_uint64, POINTER(ctypes.c_uint32), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lmx_op_score_row": (c_int32, [c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                   c_float, c_float, c_int32, ctypes.c_uint64, POINTER(ctypes.c_uint32), c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lmx_op_argmax": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
     "lmx_op_ce_loss": (c_int32, [c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_void_p]),
     "lmx_op_rmsnorm_bwd": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),

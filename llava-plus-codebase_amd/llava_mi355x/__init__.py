@@ -8,7 +8,7 @@ from .constants import IGNORE_INDEX, IMAGE_TOKEN_INDEX  # noqa: F401
 
 
 def __getattr__(name):
-    if name in ("LlavaConfig", "LlavaLlamaForCausalLM", "LlavaLlamaModel", "LmxKVCache"):
+    if name in ("LlavaConfig", "LlavaLlamaForCausalLM", "LlavaLlamaModel", "LmxKVCache", "GenerateScoresOutput"):
         from . import model
         return getattr(model, name)
     if name == "load_pretrained_model":

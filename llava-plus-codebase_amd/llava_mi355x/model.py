@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import threading
+from dataclasses import dataclass
 from typing import Sequence, Dict, List, Mapping, Optional, Tuple, Union
 
 import numpy as np
@@ -24,6 +25,7 @@ from .constants import IGNORE_INDEX, IMAGE_TOKEN_INDEX
 try:  # HF containers for the return type / config plumbing only
     from transformers import LlamaConfig
     from transformers.modeling_outputs import CausalLMOutputWithPast
+    from transformers.utils import ModelOutput
 except Exception as _e:  # pragma: no cover
     raise ImportError("transformers is required for LlamaConfig / CausalLMOutputWithPast containers") from _e
 
@@ -47,6 +49,20 @@ def _projector_kind(name: str) -> Tuple[int, int]:
     if m:
         return _C.PROJ_MLP_GELU, int(m.group(1))
     raise ValueError(f"Unknown projector type: {name}")          # multimodal_projector/builder.py:51
+
+
+@dataclass
+class GenerateScoresOutput(ModelOutput):
+    """What generate(return_dict_in_generate=True) returns (HF's GenerateDecoderOnlyOutput / GreedySearchDecoderOnlyOutput, whose name changes between
+    transformers versions, hence a class of this package's own):
+      sequences  [B, L + new]  exactly the tensor generate() returns without the argument
+      scores     with output_scores=True a tuple with one [B, V] fp32 device tensor per generated step: the row the step's token was chosen from, after the
+                 logits processors and, for a sampled request, after temperature / top-k / top-p (non-survivors -inf) — HF's `scores`; else None
+      logprobs   [B, new] fp32: log_softmax(scores[t])[token t], i.e. compute_transition_scores(sequences, scores, normalize_logits=True), always filled.
+    Divergence from HF for B > 1: a row that has stopped holds 0.0 in `scores` and `logprobs` from there on (HF goes on computing rows for the pad continuation)."""
+    sequences: torch.LongTensor = None
+    scores: Optional[Tuple[torch.FloatTensor]] = None
+    logprobs: Optional[torch.FloatTensor] = None
 
 
 class LmxKVCache:
@@ -937,18 +953,25 @@ class LlavaLlamaForCausalLM:
     @torch.no_grad()
     def generate_batch(self, prompts, images=None, max_new_tokens: int = 20, eos_token_id=None, run_ahead: int = 16,
                        prefill_chunk: int = 0, capacity: Optional[int] = None, attention_masks=None, do_sample: bool = False,
-                       temperature: float = 1.0, top_p: Optional[float] = None, top_k: Optional[int] = None, packed_prefill: bool = True, rules=None):
+                       temperature: float = 1.0, top_p: Optional[float] = None, top_k: Optional[int] = None, packed_prefill: bool = True, rules=None,
+                       score_logs: Optional[List[dict]] = None):
         """Offline batch generation (greedy, or sampled on the device): the requests are prefilled TOGETHER (own image, own prompt length — no padding: their
         rows form one packed block walked in pieces of prefill_chunk x requests rows, every linear a single GEMM per piece; lmx_prefill_batch), then
         all of them decode together, `run_ahead` chained steps per host round trip; finished requests leave the batch.  packed_prefill=False prefills
         request by request (lmx_prefill, `prefill_chunk` rows at a time).
         prompts: list of LongTensor [L_i] / [1, L_i] (with -200 markers); images: list of per-request tensors or None.
         rules: the logits processors (_rules_spec's dict of generate()'s kwargs, or its result) of every request, or a list with one entry (or None) per request.
+        score_logs: an empty list asks for the requests' score logs (lmx_seq_set_score_log): it receives one {"logprobs": [new_i] fp32 CPU tensor, "scores":
+        [new_i, V] fp32 device tensor or None} per request; put {"rows": True} in it first to get the full rows ("scores") too.
         Returns a list of LongTensor [L_i + new_i] (input ids echoed, like generate())."""
         from .batching import DecodeBatch
         self._ensure_final()
         n_req = len(prompts)
         rules = list(rules) if isinstance(rules, list) else [rules] * n_req
+        want_scores = score_logs is not None
+        score_rows = bool(want_scores and score_logs and score_logs[0].get("rows"))
+        if want_scores and self.tp_world > 1:
+            raise NotImplementedError("score logs under tensor parallelism (tp_world > 1): the follower replay does not carry them")
         if len(rules) != n_req:
             raise ValueError("generate_batch: `rules` needs one entry per request")
         images = images if images is not None else [None] * n_req
@@ -982,6 +1005,8 @@ class LlavaLlamaForCausalLM:
                 caches.append(cache)
                 self._set_stop(cache.seqs[0], self._stop_spec(eos_set))     # a member that reached EOS stops advancing inside the batched steps
                 self._set_rules(cache.seqs[0], rl, ids)
+                if want_scores and max_new_tokens > 0:
+                    self._set_score_log(cache.seqs[0], max_new_tokens, score_rows)
                 if not greedy:
                     seed = self._draw_seed()
                     check(lib.lmx_seq_set_sampling(cache.seqs[0], float(temperature), float(top_p if top_p is not None else 1.0), int(top_k or 0), seed),
@@ -1009,6 +1034,8 @@ class LlavaLlamaForCausalLM:
                                 break
                             outs[i].append(ids_steps[st][j])
                 live = [i for i in live if len(outs[i]) < budgets[i] and outs[i][-1] not in eos_set]
+            if want_scores:
+                score_logs[:] = [self._read_scores(c.seqs[0], len(o), score_rows) if max_new_tokens > 0 else self._no_scores(score_rows) for c, o in zip(caches, outs)]
             res = []
             for ids, o in zip(prompts, outs):
                 flat = ids.reshape(-1).cpu()
@@ -1025,7 +1052,9 @@ class LlavaLlamaForCausalLM:
                  max_new_tokens=None, max_length=None, streamer=None, stopping_criteria=None, use_cache=True, attention_mask=None,
                  eos_token_id=None, pad_token_id=None, input_ids=None, run_ahead: int = 16, prefill_chunk: int = 0, **kwargs):
         """Greedy / temperature+top-p generation with the device-resident decode loop (model_worker.py:174-185 contract:
-        returns LongTensor [B, L + new] that echoes the input ids, image markers included)."""
+        returns LongTensor [B, L + new] that echoes the input ids, image markers included).
+        return_dict_in_generate=True returns GenerateScoresOutput(sequences, scores, logprobs) instead: the tokens' log-probabilities, and with
+        output_scores=True HF's `scores` rows as well, recorded on the device behind each pick (lmx_seq_set_score_log); output_scores alone changes nothing."""
         if inputs is None:
             inputs = input_ids
         if inputs is None:
@@ -1043,6 +1072,17 @@ class LlavaLlamaForCausalLM:
         greedy = (not do_sample) or (temperature is not None and temperature <= 1e-5)
         # repetition_penalty, no_repeat_ngram_size, min_new_tokens / min_length, suppress_tokens, bad_words_ids: applied by the device picks (csrc/sampling.hip)
         rules = self._rules_spec(kwargs, eos_set, L)
+        # return_dict_in_generate / output_scores: the device score log (lmx_seq_set_score_log).  output_scores alone returns the plain tensor, as in HF
+        as_dict = bool(kwargs.get("return_dict_in_generate", False))
+        score_rows = as_dict and bool(kwargs.get("output_scores", False))
+        if as_dict:
+            if num_beams != 1:
+                raise NotImplementedError("return_dict_in_generate with num_beams != 1: HF returns the beams' scores and beam indices there, which the beam kernels do not keep")
+            if self.tp_world > 1:
+                raise NotImplementedError("return_dict_in_generate under tensor parallelism (tp_world > 1): the follower replay does not carry the score log")
+            if self._batcher is not None:
+                raise NotImplementedError("return_dict_in_generate with the batching scheduler on (enable_batching): its requests carry no score log")
+        score_logs: Optional[List[dict]] = [] if as_dict else None
         if rules is not None and num_beams != 1:
             raise NotImplementedError("logits processors with num_beams != 1: HF applies them to the beams' log-softmax scores, which the beam kernels do not do")
         if rules is not None and self.tp_world > 1:
@@ -1075,16 +1115,22 @@ class LlavaLlamaForCausalLM:
         row_images = self._row_images(ids, images, attention_mask)
         if B > 1 and streamer is None and not stopping_criteria and max_new_tokens > 0:
             # rows decode together (one pass over the weights per step for the whole batch)
+            batch_logs = (([{"rows": True}] if score_rows else []) if as_dict else None)
             outs = self.generate_batch([ids[b] for b in range(B)], row_images, max_new_tokens=max_new_tokens, eos_token_id=list(eos_set) or -1,
                                        run_ahead=run_ahead, prefill_chunk=prefill_chunk,
                                        attention_masks=None if attention_mask is None else [attention_mask[b] for b in range(B)],
-                                       do_sample=not greedy, temperature=temperature, top_p=top_p, top_k=top_k, rules=rules)
+                                       do_sample=not greedy, temperature=temperature, top_p=top_p, top_k=top_k, rules=rules,
+                                       score_logs=batch_logs)
             rows = [o[L:].tolist() for o in outs]
+            score_logs = batch_logs
         else:
             for b in range(B):
                 row_mask = None if attention_mask is None else attention_mask[b:b + 1]
+                log = {"rows": score_rows} if as_dict else None
                 rows.append(self._generate_one(ids[b:b + 1], row_images[b], row_mask, greedy, temperature, top_p, top_k, max_new_tokens,
-                                               eos_set, streamer, stopping_criteria, run_ahead, prefill_chunk, rules))
+                                               eos_set, streamer, stopping_criteria, run_ahead, prefill_chunk, rules, score_log=log))
+                if as_dict:
+                    score_logs.append(log)
         if streamer is not None:
             streamer.end()
         if self.tp_world > 1 and getattr(self, "p2p_active", False):
@@ -1096,7 +1142,61 @@ class LlavaLlamaForCausalLM:
         for b, r in enumerate(rows):
             out[b, :L] = ids[b].cpu()
             out[b, L:L + len(r)] = torch.tensor(r, dtype=torch.long)
+        if as_dict:
+            return self._scores_output(out.to(ids.device), score_logs, width - L, score_rows)
         return out.to(ids.device)
+
+    def _scores_output(self, sequences, logs, steps: int, with_rows: bool) -> GenerateScoresOutput:
+        """The rows' score logs as HF lays them out: `scores` a tuple over steps of [B, V], `logprobs` [B, steps]; steps past a row's stop hold 0.0."""
+        B, V = len(logs), int(self.config.vocab_size)
+        logprobs = torch.zeros((B, steps), dtype=torch.float32)
+        for b, g in enumerate(logs):
+            logprobs[b, :g["logprobs"].numel()] = g["logprobs"]
+        scores = None
+        if with_rows:
+            if B == 1:
+                block = logs[0]["scores"][None]
+            else:
+                block = torch.zeros((B, steps, V), dtype=torch.float32, device=self.device)
+                for b, g in enumerate(logs):
+                    block[b, :g["scores"].shape[0]] = g["scores"]
+            scores = tuple(block[:, t] for t in range(steps))
+        return GenerateScoresOutput(sequences=sequences, scores=scores, logprobs=logprobs.to(self.device))
+
+    @staticmethod
+    def compute_transition_scores(sequences, scores, beam_indices=None, normalize_logits: bool = False):
+        """GenerationMixin.compute_transition_scores for the outputs of generate(return_dict_in_generate=True, output_scores=True): [B, steps], entry (b, t) =
+        scores[t][b, token t of row b], after a log-softmax over each row when normalize_logits.  Plain indexing on the tensors (the device already produced
+        the normalised figures: GenerateScoresOutput.logprobs)."""
+        if beam_indices is not None:
+            raise NotImplementedError("compute_transition_scores with beam_indices: generate() keeps scores for num_beams == 1 only")
+        steps = len(scores)
+        stacked = torch.stack(tuple(scores), dim=1)                          # [B, steps, V]
+        if normalize_logits:
+            stacked = torch.log_softmax(stacked, dim=-1)
+        tok = sequences[:, sequences.shape[1] - steps:].to(stacked.device)
+        return stacked.gather(2, tok[..., None])[..., 0]
+
+    def _set_score_log(self, seq, max_new_tokens: int, with_rows: bool) -> None:
+        """Before the prefill, like the stop rule and the logits processors: token 1's row is recorded too."""
+        cap = max(1, min(int(max_new_tokens), self.s_max + 8))
+        check(lib.lmx_seq_set_score_log(seq, cap, int(bool(with_rows)), stream_handle()), "lmx_seq_set_score_log")
+
+    def _no_scores(self, with_rows: bool) -> dict:
+        return {"logprobs": torch.zeros(0, dtype=torch.float32),
+                "scores": torch.zeros((0, int(self.config.vocab_size)), dtype=torch.float32, device=self.device) if with_rows else None}
+
+    def _read_scores(self, seq, n: int, with_rows: bool) -> dict:
+        """The first n entries of the sequence's score log (the ids the request kept): log-probabilities on the CPU, rows on the device."""
+        if n <= 0:
+            return self._no_scores(with_rows)
+        host = (ctypes.c_float * n)()
+        got = ctypes.c_int32(0)
+        rows = torch.empty((n, int(self.config.vocab_size)), dtype=torch.float32, device=self.device) if with_rows else None
+        check(lib.lmx_seq_read_scores(seq, host, n, ctypes.byref(got), ptr(rows), stream_handle()), "lmx_seq_read_scores")
+        if got.value != n:
+            raise RuntimeError(f"score log: {got.value} entries recorded for {n} generated ids")
+        return {"logprobs": torch.tensor(list(host), dtype=torch.float32), "scores": rows}
 
     @staticmethod
     def _row_images(ids, images, attention_mask) -> List:
@@ -1204,7 +1304,7 @@ class LlavaLlamaForCausalLM:
         p = (ctypes.c_int64 * max(1, len(h)))(*h)
         check(lib.lmx_seq_set_logit_rules(seq, pen, ngram, min_new, e, len(eos), s, len(sup), p, len(h), stream_handle()), "lmx_seq_set_logit_rules")
 
-    def _prepare_request(self, ids, images, attention_mask, sampling, stop=None, feats=None, rules=None) -> dict:
+    def _prepare_request(self, ids, images, attention_mask, sampling, stop=None, feats=None, rules=None, score_log=None) -> dict:
         """The RANK-LOCAL half of a request's prefill: image encode (the tower is replicated here; `feats` = the (features, hashes) pair of a batch-wide
         sharded pass, _preencode_requests, replaces it), splice, selection of the valid rows, a fresh sequence with its
         sampling state.  Nothing in here carries a decoder collective, so under tensor parallelism a failure (a bad request, an allocation) can still be
@@ -1251,6 +1351,8 @@ class LlavaLlamaForCausalLM:
                       "lmx_seq_set_sampling")
             self._set_stop(cache.seqs[0], stop)          # before the prefill: its own pick (token 1) is tested too
             self._set_rules(cache.seqs[0], rules, ids)
+            if score_log is not None:
+                self._set_score_log(cache.seqs[0], *score_log)          # (max_new_tokens, with rows)
             return {"cache": cache, "embeds": embeds, "valid": valid}
         except BaseException:
             if cache is not None:
@@ -1303,11 +1405,11 @@ class LlavaLlamaForCausalLM:
         self._prefill_packed([p["cache"].seqs[0] for p in prepared], [self._packed_rows(p["embeds"], p["valid"]) for p in prepared], prefill_chunk)
         return None
 
-    def _prefill_request(self, ids, images, attention_mask, sampling, prefill_chunk: int = 0, return_logits: bool = False, stop=None, rules=None):
+    def _prefill_request(self, ids, images, attention_mask, sampling, prefill_chunk: int = 0, return_logits: bool = False, stop=None, rules=None, score_log=None):
         """Image encode + splice + prefill of ONE request (ids [1, L]) into a fresh sequence; the first pick (argmax, or a draw when
         `sampling` = (temperature, top_p, top_k, seed) is given) is on the device when the stream gets there.  Shared by the request
         thread (generate) and the scheduler threads (batching.py, tp_serving.py)."""
-        p = self._prepare_request(ids, images, attention_mask, sampling, stop, rules=rules)
+        p = self._prepare_request(ids, images, attention_mask, sampling, stop, rules=rules, score_log=score_log)
         try:
             last = self._run_prepared([p], prefill_chunk, return_logits=return_logits)
             return (p["cache"], last) if return_logits else p["cache"]
@@ -1331,8 +1433,11 @@ class LlavaLlamaForCausalLM:
             raise
 
     def _generate_one(self, ids, images, attention_mask, greedy, temperature, top_p, top_k, max_new_tokens, eos_set, streamer,
-                      stopping_criteria, run_ahead, prefill_chunk, rules=None) -> List[int]:
+                      stopping_criteria, run_ahead, prefill_chunk, rules=None, score_log: Optional[dict] = None) -> List[int]:
+        """score_log: {"rows": bool} asks for the request's score log; it receives "logprobs" / "scores" (_read_scores) for the ids returned."""
         if max_new_tokens <= 0:
+            if score_log is not None:
+                score_log.update(self._no_scores(bool(score_log.get("rows"))))
             return []
         crit = list(stopping_criteria) if stopping_criteria is not None else []
         out: List[int] = []
@@ -1377,7 +1482,8 @@ class LlavaLlamaForCausalLM:
             gate.acquire()
         try:
             sampling = None if greedy else (float(temperature), top_p, top_k, self._draw_seed())
-            cache = self._prefill_request(ids, images, attention_mask, sampling, prefill_chunk, stop=stop, rules=rules)
+            cache = self._prefill_request(ids, images, attention_mask, sampling, prefill_chunk, stop=stop, rules=rules,
+                                          score_log=None if score_log is None else (max_new_tokens, bool(score_log.get("rows"))))
             seq = cache.seqs[0]
             if gate is not None:
                 torch.cuda.current_stream(self.device).synchronize()      # the next request's prefill starts when this one is done
@@ -1416,6 +1522,8 @@ class LlavaLlamaForCausalLM:
                 ahead = max(1, min(ahead, budget - produced))
                 check(lib.lmx_decode(self._h, seq, -1, ahead, None, 1, stream_handle()), "lmx_decode")
                 produced += ahead
+            if score_log is not None:
+                score_log.update(self._read_scores(seq, len(out), bool(score_log.get("rows"))))
             return out
         finally:
             self._release_request_cache(cache, out)      # to the prefix cache (enable_reuse) or back to the pool

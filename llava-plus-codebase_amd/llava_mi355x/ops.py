@@ -226,6 +226,32 @@ def argmax(logits):
     return out
 
 
+def score_row(buf, V, history=(), n_out=0, token=-1, penalty=1.0, ngram=0, min_new=0, eos=(), suppress=(), temperature=0.0, top_p=1.0, top_k=0, seed=0,
+              u32=None, want_row=True):
+    """The score recorder (csrc/sampling.hip, lmx_op_score_row) on one row: `buf` is a device buffer of ld = buf.numel() >= V elements whose first V are the
+    raw logits; `history` the ids the logits processors see, the last n_out of them generated.  temperature <= 0: the greedy row, else the sampled one
+    (u32: the uniform number as a 32-bit integer, else Philox(seed, n_out)).  token < 0 (sampled only): score the id re-drawn under that number.
+    Returns (processed fp32 row [V] or None, lse, logprob, re-drawn id or -1) — the row on the device, the scalars as Python numbers."""
+    import ctypes
+    _need_cuda(buf)
+    dev = buf.device
+    hist = [int(t) for t in history]
+    h = torch.tensor(hist or [0], dtype=torch.long, device=dev)
+    eos, sup = [int(t) for t in eos], [int(t) for t in suppress]
+    e = (ctypes.c_int64 * max(1, len(eos)))(*eos)
+    s = (ctypes.c_int64 * max(1, len(sup)))(*sup)
+    row = torch.empty(V, dtype=torch.float32, device=dev) if want_row else None
+    out2 = torch.zeros(2, dtype=torch.float32, device=dev)
+    redraw = torch.full((1,), -1, dtype=torch.long, device=dev)
+    keep = torch.zeros(V, dtype=torch.uint8, device=dev) if temperature > 0 else None
+    uo = ctypes.pointer(ctypes.c_uint32(int(u32))) if u32 is not None else None
+    check(lib.lmx_op_score_row(torch_dtype_code(buf.dtype), ptr(buf), int(V), buf.numel(), ptr(h), len(hist), int(n_out), float(penalty), int(ngram), int(min_new),
+                               e, len(eos), s, len(sup), float(temperature), float(top_p), int(top_k), int(seed), uo, int(token), ptr(row), ptr(out2), ptr(redraw),
+                               ptr(keep), stream_handle()), "score_row")
+    lse, lp = out2.tolist()
+    return row, lse, lp, int(redraw.item())
+
+
 def im2col(pixels, patch, kpad):
     _need_cuda(pixels)
     N, C, S, _ = pixels.shape
