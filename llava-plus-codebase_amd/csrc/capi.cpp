@@ -198,10 +198,7 @@ int lmx_seq_create(lmx_model* m, lmx_seq** out) {
         // Stale K / V rows stay (any values, NaN / Inf included: every kernel masks by length, tests/test_attn_cache_tails_gpu.py), only the state words are cleared.
         if (s->impl.ev_idle) LMX_CHECK_HIP(hipEventSynchronize(s->impl.ev_idle));
         s->impl.len = 0;
-        s->impl.samp = SampleParams{};
-        s->impl.clear_logit_rules();
-        s->impl.clear_score_log();
-        s->impl.uid = next_seq_uid();
+        s->impl.end_request();
         zero_fill(s->impl.state.p, 16);
         zero_fill(s->impl.stopbuf.p, sizeof(StopSpec));
     } else {
@@ -216,8 +213,7 @@ int lmx_seq_destroy(lmx_seq* s) {
     if (!s) return 0;
     Model* m = s->impl.m;
     if (m) m->live_seqs.fetch_sub(1, std::memory_order_relaxed);
-    s->impl.clear_logit_rules();          // a pooled sequence carries no request's logits processors
-    s->impl.clear_score_log();            // ... and records no scores for the next request
+    s->impl.end_request();                // a pooled sequence carries no request's sampler, logits processors or score log
     bool pooled = false;
     bool idle_known = true;
     if (m && s->impl.used) {
@@ -275,12 +271,17 @@ int lmx_seq_stopped(lmx_seq* s, int32_t* out, void* stream) {
     *out = done != 0;
     LMX_API_END
 }
+// (temperature, top_p, top_k, seed) of the C ABI as the kernels take them.  clamp: temperature <= 0 means greedy and is stored as 0; lmx_op_sample alone
+// hands the value through as given
+static SampleParams make_sample_params(float temperature, float top_p, int32_t top_k, uint64_t seed, bool clamp = true) {
+    return SampleParams{clamp && !(temperature > 0.f) ? 0.f : temperature, top_p, top_k, (uint32_t)seed, (uint32_t)(seed >> 32)};
+}
 int lmx_seq_set_sampling(lmx_seq* s, float temperature, float top_p, int32_t top_k, uint64_t seed) {
     LMX_API_BEGIN
     LMX_REQUIRE(s, "null sequence");
     LMX_REQUIRE(temperature <= 0.f || (top_p > 0.f && top_p <= 1.f), "top_p must be in (0, 1]");
     LMX_REQUIRE(top_k >= 0, "top_k must be >= 0 (0 = off)");
-    s->impl.samp = SampleParams{temperature > 0.f ? temperature : 0.f, top_p, top_k, (uint32_t)seed, (uint32_t)(seed >> 32)};
+    s->impl.samp = make_sample_params(temperature, top_p, top_k, seed);
     s->impl.uid = next_seq_uid();          // a decode batch holding this sequence rebuilds its table entry
     LMX_API_END
 }
@@ -315,7 +316,7 @@ int lmx_op_pick_rules(int32_t dtype, const void* logits_dev, int32_t V, int32_t 
     LMX_REQUIRE(n_out >= 0 && n_out <= n_hist, "pick_rules: n_out counts the generated ids at the end of the history");
     LogitRules r = make_rules(repetition_penalty, no_repeat_ngram, min_new_tokens, eos_ids, n_eos, suppress_ids, n_suppress, n_hist);
     r.prompt = history_dev;
-    launch_pick_rules(dtype, logits_dev, V, r, nullptr, 0, nullptr, n_out, SampleParams{temperature > 0.f ? temperature : 0.f, top_p, top_k, (uint32_t)seed, (uint32_t)(seed >> 32)},
+    launch_pick_rules(dtype, logits_dev, V, r, nullptr, 0, nullptr, n_out, make_sample_params(temperature, top_p, top_k, seed),
                       u32_override_host, out_tok_dev, processed_row_dev, keep_out_dev, S(stream));
     LMX_API_END
 }
@@ -357,14 +358,14 @@ int lmx_op_score_row(int32_t dtype, const void* logits_dev, int32_t V, int32_t l
     LMX_REQUIRE(n_out >= 0 && n_out <= n_hist, "score_row: n_out counts the generated ids at the end of the history");
     LogitRules r = make_rules(repetition_penalty, no_repeat_ngram, min_new_tokens, eos_ids, n_eos, suppress_ids, n_suppress, n_hist);
     r.prompt = history_dev;
-    launch_score_row(dtype, logits_dev, V, r, n_out, SampleParams{temperature > 0.f ? temperature : 0.f, top_p, top_k, (uint32_t)seed, (uint32_t)(seed >> 32)},
+    launch_score_row(dtype, logits_dev, V, r, n_out, make_sample_params(temperature, top_p, top_k, seed),
                      u32_override_host, token, keep_scratch_dev, row_out_dev, lse_logprob_dev, redraw_tok_dev, S(stream));
     LMX_API_END
 }
 int lmx_op_sample(int32_t dtype, const void* logits_dev, int32_t V, float temperature, float top_p, int32_t top_k, uint64_t seed,
                   const int32_t* offset_dev, const uint32_t* u32_override_host, int64_t* out_tok_dev, uint8_t* keep_out_dev, void* stream) {
     LMX_API_BEGIN
-    launch_sample(dtype, logits_dev, V, SampleParams{temperature, top_p, top_k, (uint32_t)seed, (uint32_t)(seed >> 32)}, offset_dev, out_tok_dev,
+    launch_sample(dtype, logits_dev, V, make_sample_params(temperature, top_p, top_k, seed, /*clamp=*/false), offset_dev, out_tok_dev,
                   u32_override_host, keep_out_dev, S(stream));
     LMX_API_END
 }
@@ -374,8 +375,7 @@ int lmx_seq_reset(lmx_seq* s) {
     s->impl.len = 0;
     zero_fill(s->impl.state.p, 16);       // caller guarantees no work on this sequence is in flight
     zero_fill(&s->impl.d_stop->done, sizeof(int));      // a sequence that stopped by its id rule is live again (the rule itself stays until the next set_stop)
-    s->impl.clear_logit_rules();                        // the logits processors belong to the request that set them
-    s->impl.clear_score_log();                          // and so does the score log
+    s->impl.end_request(/*keep_sampling=*/true);        // the logits processors and the score log belong to the request that set them; the sampler stays
     LMX_API_END
 }
 int lmx_seq_length(const lmx_seq* s) { return s ? s->impl.len : -1; }
@@ -874,10 +874,7 @@ int lmx_seq_truncate(lmx_seq* s, int32_t n_rows, void* stream) {
     // a finished request's sequence starts another request that shares its first n_rows positions (prefix reuse): keep K / V^T rows [0, n_rows), forget the
     // rest of the request — position, token log, sampling parameters, stop rule (ordered on `stream` behind whatever still runs on the sequence)
     s->impl.len = n_rows;
-    s->impl.samp = SampleParams{};
-    s->impl.clear_logit_rules();
-    s->impl.clear_score_log();
-    s->impl.uid = next_seq_uid();
+    s->impl.end_request();
     s->impl.last_stream = S(stream); s->impl.used = true;
     launch_set_state(s->impl.d_len, n_rows, s->impl.d_tok, 0, 1, s->impl.d_nout, 0, S(stream));
     launch_set_stop(s->impl.d_stop, StopSpec{}, S(stream));

@@ -219,6 +219,14 @@ struct Seq {
     }
     void set_score_log(int cap, bool want_rows, hipStream_t st);      // cap 0 detaches
     void clear_score_log() { if (score_cap > 0) { score_cap = 0; score_rows_on = false; uid = next_seq_uid(); } }
+    // The end of a request's HOST-side state, in one place for the four entry points that end one (the recycled branch of lmx_seq_create, lmx_seq_destroy,
+    // lmx_seq_truncate; lmx_seq_reset with keep_sampling): sampling parameters, logits processors, score log, and a new uid so that a Batch holding the
+    // sequence rebuilds its table entry.  The device-side words (position, token log, stop rule and flag) stay with each entry point: they differ on purpose
+    void end_request(bool keep_sampling = false) {
+        if (!keep_sampling) samp = SampleParams{};
+        clear_logit_rules(); clear_score_log();
+        uid = next_seq_uid();
+    }
     DevBuf pws;                        // prefill workspace
     DevBuf skw;                        // split-K partial tiles of the ping-pong GEMM (o_proj, down_proj of a prefill)
     DevBuf dws;                        // decode workspace

@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes
 import threading
 from dataclasses import dataclass
-from typing import Sequence, Dict, List, Mapping, Optional, Tuple, Union
+from typing import Sequence, Dict, List, Mapping, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -63,6 +63,20 @@ class GenerateScoresOutput(ModelOutput):
     sequences: torch.LongTensor = None
     scores: Optional[Tuple[torch.FloatTensor]] = None
     logprobs: Optional[torch.FloatTensor] = None
+
+
+class RequestOptions(NamedTuple):
+    """What one request puts on its engine sequence before its prefill (_apply_request_options); None = not set.  sampling: (temperature, top_p, top_k,
+    seed); stop: _stop_spec's result; rules: _rules_spec's result; score_log: (capacity in tokens, with rows)."""
+    sampling: Optional[tuple] = None
+    stop: Optional[tuple] = None
+    rules: Optional[tuple] = None
+    score_log: Optional[tuple] = None
+
+    @classmethod
+    def from_request(cls, r: Mapping) -> "RequestOptions":
+        """From a scheduler request dict (batching.py), also after the wire (tp_serving.CommandChannel.wire_request turns tuples into lists)."""
+        return cls(*(None if r.get(k) is None else tuple(r[k]) for k in cls._fields))
 
 
 class LmxKVCache:
@@ -954,22 +968,21 @@ class LlavaLlamaForCausalLM:
     def generate_batch(self, prompts, images=None, max_new_tokens: int = 20, eos_token_id=None, run_ahead: int = 16,
                        prefill_chunk: int = 0, capacity: Optional[int] = None, attention_masks=None, do_sample: bool = False,
                        temperature: float = 1.0, top_p: Optional[float] = None, top_k: Optional[int] = None, packed_prefill: bool = True, rules=None,
-                       score_logs: Optional[List[dict]] = None):
+                       score_rows: Optional[bool] = None):
         """Offline batch generation (greedy, or sampled on the device): the requests are prefilled TOGETHER (own image, own prompt length — no padding: their
         rows form one packed block walked in pieces of prefill_chunk x requests rows, every linear a single GEMM per piece; lmx_prefill_batch), then
         all of them decode together, `run_ahead` chained steps per host round trip; finished requests leave the batch.  packed_prefill=False prefills
         request by request (lmx_prefill, `prefill_chunk` rows at a time).
         prompts: list of LongTensor [L_i] / [1, L_i] (with -200 markers); images: list of per-request tensors or None.
         rules: the logits processors (_rules_spec's dict of generate()'s kwargs, or its result) of every request, or a list with one entry (or None) per request.
-        score_logs: an empty list asks for the requests' score logs (lmx_seq_set_score_log): it receives one {"logprobs": [new_i] fp32 CPU tensor, "scores":
-        [new_i, V] fp32 device tensor or None} per request; put {"rows": True} in it first to get the full rows ("scores") too.
-        Returns a list of LongTensor [L_i + new_i] (input ids echoed, like generate())."""
+        score_rows: not None asks for the requests' score logs (lmx_seq_set_score_log), True with the full rows: one {"logprobs": [new_i] fp32 CPU tensor,
+        "scores": [new_i, V] fp32 device tensor or None} per request.
+        Returns a list of LongTensor [L_i + new_i] (input ids echoed, like generate()); with score_rows not None (that list, the score logs)."""
         from .batching import DecodeBatch
         self._ensure_final()
         n_req = len(prompts)
         rules = list(rules) if isinstance(rules, list) else [rules] * n_req
-        want_scores = score_logs is not None
-        score_rows = bool(want_scores and score_logs and score_logs[0].get("rows"))
+        want_scores = score_rows is not None
         if want_scores and self.tp_world > 1:
             raise NotImplementedError("score logs under tensor parallelism (tp_world > 1): the follower replay does not carry them")
         if len(rules) != n_req:
@@ -984,6 +997,8 @@ class LlavaLlamaForCausalLM:
             masks = attention_masks if attention_masks is not None else [None] * n_req
             # tensor parallel: the images of ALL requests through one tower pass split over the ranks (every rank runs this same plan)
             pre = self._preencode_requests(images) if self.tp_world > 1 else [None] * n_req
+            stop = self._stop_spec(eos_set)     # a member that reached EOS stops advancing inside the batched steps
+            score_log = (max_new_tokens, score_rows) if want_scores and max_new_tokens > 0 else None
             for ids, img, am, ov, rl in zip(prompts, images, masks, pre, rules):
                 ids = ids if ids.dim() == 2 else ids[None]
                 if isinstance(rl, dict):
@@ -991,30 +1006,13 @@ class LlavaLlamaForCausalLM:
                 if rl is not None and self.tp_world > 1:
                     raise NotImplementedError("logits processors under tensor parallelism: the follower replay does not carry them")
                 am = None if am is None else (am if am.dim() == 2 else am[None])
-                self._tls.plan_mask = None
-                self._tls.feats_override = ov
-                try:
-                    _, _, mask, _, embeds, _ = self.prepare_inputs_labels_for_multimodal(ids, None, am, None, None, img)
-                finally:
-                    self._tls.feats_override = None
-                if embeds is None:
-                    embeds = self.get_model().embed_tokens(ids.to(self.device)); valid = None if am is None else am.bool()
-                else:
-                    valid = self._tls.plan_mask if mask is None else mask.bool()
-                cache = LmxKVCache(self, 1)
-                caches.append(cache)
-                self._set_stop(cache.seqs[0], self._stop_spec(eos_set))     # a member that reached EOS stops advancing inside the batched steps
-                self._set_rules(cache.seqs[0], rl, ids)
-                if want_scores and max_new_tokens > 0:
-                    self._set_score_log(cache.seqs[0], max_new_tokens, score_rows)
-                if not greedy:
-                    seed = self._draw_seed()
-                    check(lib.lmx_seq_set_sampling(cache.seqs[0], float(temperature), float(top_p if top_p is not None else 1.0), int(top_k or 0), seed),
-                          "lmx_seq_set_sampling")
+                opts = RequestOptions(None if greedy else (temperature, top_p, top_k, self._draw_seed()), stop, rl, score_log)
+                p = self._prepare_request(ids, img, am, opts, feats=ov, reuse=False)      # no prefix reuse here: the caches are closed below
+                caches.append(p["cache"])
                 if packed_prefill:
-                    packed.append(self._packed_rows(embeds, valid))
+                    packed.append(self._packed_rows(p["embeds"], p["valid"]))
                 else:
-                    self._prefill_rows(cache, embeds, valid, want_all=False, greedy=True, chunk=prefill_chunk)
+                    self._prefill_rows(p["cache"], p["embeds"], p["valid"], want_all=False, greedy=True, chunk=prefill_chunk)
             if packed_prefill:
                 self._prefill_packed([c.seqs[0] for c in caches], packed, prefill_chunk)
             for cache in caches:
@@ -1034,13 +1032,12 @@ class LlavaLlamaForCausalLM:
                                 break
                             outs[i].append(ids_steps[st][j])
                 live = [i for i in live if len(outs[i]) < budgets[i] and outs[i][-1] not in eos_set]
-            if want_scores:
-                score_logs[:] = [self._read_scores(c.seqs[0], len(o), score_rows) if max_new_tokens > 0 else self._no_scores(score_rows) for c, o in zip(caches, outs)]
+            logs = [self._read_scores(c.seqs[0], len(o), score_rows) if score_log else self._no_scores(score_rows) for c, o in zip(caches, outs)] if want_scores else None
             res = []
             for ids, o in zip(prompts, outs):
                 flat = ids.reshape(-1).cpu()
                 res.append(torch.cat([flat, torch.tensor(o, dtype=torch.long)]).to(self.device))
-            return res
+            return (res, logs) if want_scores else res
         finally:
             batch.close()
             for c in caches:
@@ -1082,7 +1079,7 @@ class LlavaLlamaForCausalLM:
                 raise NotImplementedError("return_dict_in_generate under tensor parallelism (tp_world > 1): the follower replay does not carry the score log")
             if self._batcher is not None:
                 raise NotImplementedError("return_dict_in_generate with the batching scheduler on (enable_batching): its requests carry no score log")
-        score_logs: Optional[List[dict]] = [] if as_dict else None
+        score_logs: List[dict] = []
         if rules is not None and num_beams != 1:
             raise NotImplementedError("logits processors with num_beams != 1: HF applies them to the beams' log-softmax scores, which the beam kernels do not do")
         if rules is not None and self.tp_world > 1:
@@ -1115,22 +1112,23 @@ class LlavaLlamaForCausalLM:
         row_images = self._row_images(ids, images, attention_mask)
         if B > 1 and streamer is None and not stopping_criteria and max_new_tokens > 0:
             # rows decode together (one pass over the weights per step for the whole batch)
-            batch_logs = (([{"rows": True}] if score_rows else []) if as_dict else None)
             outs = self.generate_batch([ids[b] for b in range(B)], row_images, max_new_tokens=max_new_tokens, eos_token_id=list(eos_set) or -1,
                                        run_ahead=run_ahead, prefill_chunk=prefill_chunk,
                                        attention_masks=None if attention_mask is None else [attention_mask[b] for b in range(B)],
                                        do_sample=not greedy, temperature=temperature, top_p=top_p, top_k=top_k, rules=rules,
-                                       score_logs=batch_logs)
+                                       score_rows=score_rows if as_dict else None)
+            if as_dict:
+                outs, score_logs = outs
             rows = [o[L:].tolist() for o in outs]
-            score_logs = batch_logs
         else:
+            # the request's options but for the stop rule and the sampler's seed, which _generate_one adds
+            opts = RequestOptions(None if greedy else (float(temperature), top_p, top_k, None), None, rules, (max_new_tokens, score_rows) if as_dict else None)
             for b in range(B):
                 row_mask = None if attention_mask is None else attention_mask[b:b + 1]
-                log = {"rows": score_rows} if as_dict else None
-                rows.append(self._generate_one(ids[b:b + 1], row_images[b], row_mask, greedy, temperature, top_p, top_k, max_new_tokens,
-                                               eos_set, streamer, stopping_criteria, run_ahead, prefill_chunk, rules, score_log=log))
-                if as_dict:
-                    score_logs.append(log)
+                row, log = self._generate_one(ids[b:b + 1], row_images[b], row_mask, opts, max_new_tokens, eos_set, streamer, stopping_criteria, run_ahead,
+                                              prefill_chunk)
+                rows.append(row)
+                score_logs.append(log)
         if streamer is not None:
             streamer.end()
         if self.tp_world > 1 and getattr(self, "p2p_active", False):
@@ -1176,11 +1174,6 @@ class LlavaLlamaForCausalLM:
             stacked = torch.log_softmax(stacked, dim=-1)
         tok = sequences[:, sequences.shape[1] - steps:].to(stacked.device)
         return stacked.gather(2, tok[..., None])[..., 0]
-
-    def _set_score_log(self, seq, max_new_tokens: int, with_rows: bool) -> None:
-        """Before the prefill, like the stop rule and the logits processors: token 1's row is recorded too."""
-        cap = max(1, min(int(max_new_tokens), self.s_max + 8))
-        check(lib.lmx_seq_set_score_log(seq, cap, int(bool(with_rows)), stream_handle()), "lmx_seq_set_score_log")
 
     def _no_scores(self, with_rows: bool) -> dict:
         return {"logprobs": torch.zeros(0, dtype=torch.float32),
@@ -1245,16 +1238,6 @@ class LlavaLlamaForCausalLM:
             kws = []
         return (eos, kws) if (eos or kws) else None
 
-    def _set_stop(self, seq, spec) -> None:
-        if not spec:
-            return
-        eos, kws = spec
-        e = (ctypes.c_int64 * max(1, len(eos)))(*eos)
-        flat = [v for k in kws for v in k]
-        f = (ctypes.c_int64 * max(1, len(flat)))(*flat)
-        ln = (ctypes.c_int32 * max(1, len(kws)))(*[len(k) for k in kws])
-        check(lib.lmx_seq_set_stop(seq, e, len(eos), f, ln, len(kws), stream_handle()), "lmx_seq_set_stop")
-
     @staticmethod
     def _rules_spec(kw: Mapping, eos_set, prompt_len: int):
         """generate()'s logits-processor arguments in the form lmx_seq_set_logit_rules takes them: (repetition_penalty, no_repeat_ngram_size, min_new_tokens,
@@ -1293,21 +1276,37 @@ class LlavaLlamaForCausalLM:
             return None
         return (float(pen), int(ngram), int(min_new), eos, sup)
 
-    def _set_rules(self, seq, rules, ids) -> None:
-        """Before the prefill, like the stop rule: token 1 follows the rules too.  `ids`: the row's input_ids as passed in (markers and padding included)."""
-        if not rules:
+    def _apply_request_options(self, seq, ids, opts: Optional[RequestOptions]) -> None:
+        """The one place that puts a request's options on its sequence, all BEFORE the prefill: its own pick (token 1) is drawn, tested against the stop rule,
+        ruled and recorded like every later one.  Order on the stream: sampling (host only), stop, rules, score log.  `ids`: the row's input_ids as passed in
+        (markers and padding included), the history the rules start from."""
+        if opts is None:
             return
-        pen, ngram, min_new, eos, sup = rules
-        h = [int(v) for v in ids.reshape(-1).tolist()]
-        e = (ctypes.c_int64 * max(1, len(eos)))(*eos)
-        s = (ctypes.c_int64 * max(1, len(sup)))(*sup)
-        p = (ctypes.c_int64 * max(1, len(h)))(*h)
-        check(lib.lmx_seq_set_logit_rules(seq, pen, ngram, min_new, e, len(eos), s, len(sup), p, len(h), stream_handle()), "lmx_seq_set_logit_rules")
+        st = stream_handle()
 
-    def _prepare_request(self, ids, images, attention_mask, sampling, stop=None, feats=None, rules=None, score_log=None) -> dict:
+        def i64(vals):
+            return (ctypes.c_int64 * max(1, len(vals)))(*vals)
+        if opts.sampling is not None:
+            # the draw happens on the device (csrc/sampling.hip): temperature -> top-k -> top-p -> multinomial, keyed by a seed
+            # taken from torch's CPU generator (so torch.manual_seed makes a request reproducible)
+            temperature, top_p, top_k, seed = opts.sampling
+            check(lib.lmx_seq_set_sampling(seq, float(temperature), float(top_p if top_p is not None else 1.0), int(top_k or 0), int(seed)), "lmx_seq_set_sampling")
+        if opts.stop:
+            eos, kws = opts.stop
+            lens = (ctypes.c_int32 * max(1, len(kws)))(*[len(k) for k in kws])
+            check(lib.lmx_seq_set_stop(seq, i64(eos), len(eos), i64([v for k in kws for v in k]), lens, len(kws), st), "lmx_seq_set_stop")
+        if opts.rules:
+            pen, ngram, min_new, eos, sup = opts.rules
+            h = [int(v) for v in ids.reshape(-1).tolist()]
+            check(lib.lmx_seq_set_logit_rules(seq, pen, ngram, min_new, i64(eos), len(eos), i64(sup), len(sup), i64(h), len(h), st), "lmx_seq_set_logit_rules")
+        if opts.score_log is not None:
+            cap, with_rows = opts.score_log
+            check(lib.lmx_seq_set_score_log(seq, max(1, min(int(cap), self.s_max + 8)), int(bool(with_rows)), st), "lmx_seq_set_score_log")
+
+    def _prepare_request(self, ids, images, attention_mask, opts: Optional[RequestOptions] = None, feats=None, reuse: bool = True) -> dict:
         """The RANK-LOCAL half of a request's prefill: image encode (the tower is replicated here; `feats` = the (features, hashes) pair of a batch-wide
-        sharded pass, _preencode_requests, replaces it), splice, selection of the valid rows, a fresh sequence with its
-        sampling state.  Nothing in here carries a decoder collective, so under tensor parallelism a failure (a bad request, an allocation) can still be
+        sharded pass, _preencode_requests, replaces it), splice, selection of the valid rows, a fresh sequence (reuse=False: never one of the prefix cache's)
+        with the request's options.  Nothing in here carries a decoder collective, so under tensor parallelism a failure (a bad request, an allocation) can still be
         agreed on by all ranks before the collective-bearing half runs (tp_serving.prefill_symmetric).  Returns {cache, embeds, valid}."""
         cache = None
         try:
@@ -1325,7 +1324,7 @@ class LlavaLlamaForCausalLM:
                 valid = self._tls.plan_mask if mask is None else mask.bool()
             # prefix reuse (reuse.PrefixCache): a finished request's sequence whose first rows are this request's first rows
             keys, reused = None, 0
-            if self._prefix is not None and embeds.shape[0] == 1 and (valid is None or bool(valid.all())):
+            if reuse and self._prefix is not None and embeds.shape[0] == 1 and (valid is None or bool(valid.all())):
                 keys = self._request_row_keys(ids, embeds.shape[1])
             if keys is not None:
                 holder, n_common = self._prefix.take(keys)
@@ -1343,16 +1342,7 @@ class LlavaLlamaForCausalLM:
             if reused:
                 embeds = embeds[:, reused:]
                 valid = None
-            if sampling is not None:
-                # the draw happens on the device (csrc/sampling.hip): temperature -> top-k -> top-p -> multinomial, keyed by a seed
-                # taken from torch's CPU generator (so torch.manual_seed makes a request reproducible)
-                temperature, top_p, top_k, seed = sampling
-                check(lib.lmx_seq_set_sampling(cache.seqs[0], float(temperature), float(top_p if top_p is not None else 1.0), int(top_k or 0), int(seed)),
-                      "lmx_seq_set_sampling")
-            self._set_stop(cache.seqs[0], stop)          # before the prefill: its own pick (token 1) is tested too
-            self._set_rules(cache.seqs[0], rules, ids)
-            if score_log is not None:
-                self._set_score_log(cache.seqs[0], *score_log)          # (max_new_tokens, with rows)
+            self._apply_request_options(cache.seqs[0], ids, opts)
             return {"cache": cache, "embeds": embeds, "valid": valid}
         except BaseException:
             if cache is not None:
@@ -1405,11 +1395,11 @@ class LlavaLlamaForCausalLM:
         self._prefill_packed([p["cache"].seqs[0] for p in prepared], [self._packed_rows(p["embeds"], p["valid"]) for p in prepared], prefill_chunk)
         return None
 
-    def _prefill_request(self, ids, images, attention_mask, sampling, prefill_chunk: int = 0, return_logits: bool = False, stop=None, rules=None, score_log=None):
+    def _prefill_request(self, ids, images, attention_mask, opts: Optional[RequestOptions] = None, prefill_chunk: int = 0, return_logits: bool = False):
         """Image encode + splice + prefill of ONE request (ids [1, L]) into a fresh sequence; the first pick (argmax, or a draw when
-        `sampling` = (temperature, top_p, top_k, seed) is given) is on the device when the stream gets there.  Shared by the request
+        opts.sampling is given) is on the device when the stream gets there.  Shared by the request
         thread (generate) and the scheduler threads (batching.py, tp_serving.py)."""
-        p = self._prepare_request(ids, images, attention_mask, sampling, stop, rules=rules, score_log=score_log)
+        p = self._prepare_request(ids, images, attention_mask, opts)
         try:
             last = self._run_prepared([p], prefill_chunk, return_logits=return_logits)
             return (p["cache"], last) if return_logits else p["cache"]
@@ -1419,12 +1409,11 @@ class LlavaLlamaForCausalLM:
 
     def _prefill_requests(self, reqs: Sequence[dict], prefill_chunk: int = 0) -> List["LmxKVCache"]:
         """Several requests prefilled TOGETHER (lmx_prefill_batch: one GEMM per linear over the packed rows of all of them).  reqs: dicts with ids [1, L],
-        images, attention_mask, sampling (as _prefill_request takes them).  One request takes the single-sequence path (same bits as generate())."""
+        images, attention_mask and the options' keys (RequestOptions.from_request).  One request takes the single-sequence path (same bits as generate())."""
         prepared: List[dict] = []
         try:
             for r in reqs:
-                prepared.append(self._prepare_request(r["ids"].to(self.device), r["images"], r["attention_mask"], r["sampling"], r.get("stop"),
-                                                      rules=r.get("rules")))
+                prepared.append(self._prepare_request(r["ids"].to(self.device), r["images"], r["attention_mask"], RequestOptions.from_request(r)))
             self._run_prepared(prepared, prefill_chunk)
             return [p["cache"] for p in prepared]
         except BaseException:
@@ -1432,13 +1421,12 @@ class LlavaLlamaForCausalLM:
                 p["cache"].close()
             raise
 
-    def _generate_one(self, ids, images, attention_mask, greedy, temperature, top_p, top_k, max_new_tokens, eos_set, streamer,
-                      stopping_criteria, run_ahead, prefill_chunk, rules=None, score_log: Optional[dict] = None) -> List[int]:
-        """score_log: {"rows": bool} asks for the request's score log; it receives "logprobs" / "scores" (_read_scores) for the ids returned."""
+    def _generate_one(self, ids, images, attention_mask, opts: RequestOptions, max_new_tokens, eos_set, streamer, stopping_criteria, run_ahead,
+                      prefill_chunk) -> Tuple[List[int], Optional[dict]]:
+        """opts: the request's options without a stop rule and with no seed in `sampling` yet: both are completed here.  Returns the new ids and, when
+        opts.score_log asks for it, the score log's "logprobs" / "scores" (_read_scores) for them, else None."""
         if max_new_tokens <= 0:
-            if score_log is not None:
-                score_log.update(self._no_scores(bool(score_log.get("rows"))))
-            return []
+            return [], (None if opts.score_log is None else self._no_scores(opts.score_log[1]))
         crit = list(stopping_criteria) if stopping_criteria is not None else []
         out: List[int] = []
 
@@ -1464,26 +1452,25 @@ class LlavaLlamaForCausalLM:
             # the scheduler thread prefills: under tensor parallelism because every call that carries a collective must be issued in an order the
             # leader broadcasts to the followers first (tp_serving.py); on one GPU (packed_prefill) because the requests waiting at that moment are
             # prefilled TOGETHER, one GEMM per linear over all their rows (lmx_prefill_batch).  The request thread hands the request over and waits
-            sampling = None if greedy else (float(temperature), top_p, top_k, int(torch.randint(0, 2 ** 62, (1,)).item()))
+            sampling = opts.sampling and opts.sampling[:3] + (int(torch.randint(0, 2 ** 62, (1,)).item()),)
             request = {"ids": ids.cpu(), "images": images, "attention_mask": None if attention_mask is None else attention_mask.cpu(),
-                       "sampling": sampling, "prefill_chunk": int(prefill_chunk), "stop": stop, "rules": rules, "out_ref": out}
+                       "sampling": sampling, "prefill_chunk": int(prefill_chunk), "stop": stop, "rules": opts.rules, "out_ref": out}
             if getattr(batcher, "prepare_on_request_thread", False) and batcher.queued() < batcher.capacity:      # (a prepared request holds a sequence: bounded)
                 # the rank-local half of the prefill here, on this request's own thread and stream (beside the running decode steps and the other requests'
                 # prefills): image encode or feature-cache hit, splice, prefix-cache take.  The prefill thread then packs ready rows only
-                prepared = self._prepare_request(ids.to(self.device), images, attention_mask, sampling, stop, rules=rules)
+                prepared = self._prepare_request(ids.to(self.device), images, attention_mask, RequestOptions.from_request(request))
                 request["prepared"], request["rows"] = prepared, int(prepared["embeds"].shape[1])
                 # (from here the scheduler owns the prepared sequence: it closes it if the request never reaches a prefill)
             batcher.submit_request(request, make_emit, int(max_new_tokens))
-            return out
+            return out, None
         # With the batching scheduler on, image encode + prefill of concurrent requests run one at a time: k prefills sharing the GPU
         # all finish late (time to first token = k x one prefill for everybody), one after the other finishes the first after one.
         gate = self._prefill_gate if batcher is not None else None
         if gate is not None:
             gate.acquire()
         try:
-            sampling = None if greedy else (float(temperature), top_p, top_k, self._draw_seed())
-            cache = self._prefill_request(ids, images, attention_mask, sampling, prefill_chunk, stop=stop, rules=rules,
-                                          score_log=None if score_log is None else (max_new_tokens, bool(score_log.get("rows"))))
+            opts = opts._replace(sampling=opts.sampling and opts.sampling[:3] + (self._draw_seed(),), stop=stop)
+            cache = self._prefill_request(ids, images, attention_mask, opts, prefill_chunk)
             seq = cache.seqs[0]
             if gate is not None:
                 torch.cuda.current_stream(self.device).synchronize()      # the next request's prefill starts when this one is done
@@ -1505,7 +1492,7 @@ class LlavaLlamaForCausalLM:
                 check(lib.lmx_seq_read_tokens(seq, host1, 1, ctypes.byref(n1), stream_handle()), "read_tokens")
                 if not emit(int(host1[0])):
                     batcher.submit(seq, emit, room=budget - 1)
-                return out
+                return out, None
             host = (ctypes.c_int64 * (budget + 1))()
             n = ctypes.c_int32(0)
             done, consumed = False, 0
@@ -1522,9 +1509,7 @@ class LlavaLlamaForCausalLM:
                 ahead = max(1, min(ahead, budget - produced))
                 check(lib.lmx_decode(self._h, seq, -1, ahead, None, 1, stream_handle()), "lmx_decode")
                 produced += ahead
-            if score_log is not None:
-                score_log.update(self._read_scores(seq, len(out), bool(score_log.get("rows"))))
-            return out
+            return out, (None if opts.score_log is None else self._read_scores(seq, len(out), opts.score_log[1]))
         finally:
             self._release_request_cache(cache, out)      # to the prefix cache (enable_reuse) or back to the pool
 

@@ -34,6 +34,7 @@ import torch
 
 from ._C import check, lib, stream_handle
 from .batching import DecodeBatch
+from .model import RequestOptions
 
 
 class CommandChannel:
@@ -144,9 +145,8 @@ def prefill_symmetric(model, channel: CommandChannel, reqs, chunk: int) -> list:
     prepared = []
     for r, f in zip(reqs, feats):
         try:
-            imgs = r["images"]
             kw = {} if f is None else {"feats": f}
-            prepared.append(model._prepare_request(r["ids"].to(model.device), imgs, r["attention_mask"], r["sampling"], r.get("stop"), **kw))
+            prepared.append(model._prepare_request(r["ids"].to(model.device), r["images"], r["attention_mask"], RequestOptions.from_request(r), **kw))
         except BaseException as e:  # noqa: BLE001
             prepared.append(e)
     ok_all = channel.agree([not isinstance(p, BaseException) for p in prepared])

@@ -97,9 +97,10 @@ def test_sequences_unchanged_and_shapes(tiny, plain_scored, name):
 def test_recorded_rows_are_the_raw_logits_at_the_c_abi(tiny):
     """Greedy, no rules: the recorded row of every step is the step's logits row upcast to fp32, bit for bit — the prefill's returned row, then lmx_decode's."""
     from llava_mi355x import _C
+    from llava_mi355x.model import RequestOptions
     model, cfg, ids, pix = tiny
     V, steps = cfg.vocab_size, 6
-    cache, first = model._prefill_request(ids, pix, None, None, return_logits=True, score_log=(steps + 1, True))
+    cache, first = model._prefill_request(ids, pix, None, RequestOptions(score_log=(steps + 1, True)), return_logits=True)
     try:
         seq = cache.seqs[0]
         bufs = []
@@ -252,6 +253,7 @@ def test_batch_of_three_with_an_early_stop(tiny, plain_scored):
 
 def test_device_stop_records_nothing_past_it(tiny, plain_scored):
     from llava_mi355x import _C
+    from llava_mi355x.model import RequestOptions
     model, _, ids, pix = tiny
     L = ids.shape[1]
     row0 = plain_scored.sequences[0, L:].tolist()
@@ -260,7 +262,7 @@ def test_device_stop_records_nothing_past_it(tiny, plain_scored):
     assert out.sequences.shape[1] == L + k + 1 and len(out.scores) == k + 1 and out.logprobs.shape == (1, k + 1)
     assert torch.equal(_bits(out.logprobs), _bits(plain_scored.logprobs[:, :k + 1]))
     # at the C ABI: steps queued past the stop leave the log where the stop left it
-    cache = model._prefill_request(ids, pix, None, None, stop=([row0[k]], []), score_log=(N_NEW, False))
+    cache = model._prefill_request(ids, pix, None, RequestOptions(stop=([row0[k]], []), score_log=(N_NEW, False)))
     try:
         seq = cache.seqs[0]
         _C.check(_C.lib.lmx_decode(model._h, seq, -1, N_NEW - 1, None, 1, _C.stream_handle()), "lmx_decode")

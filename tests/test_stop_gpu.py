@@ -41,6 +41,11 @@ def _stopped(seq):
     return bool(f.value)
 
 
+def _stop(spec):
+    from llava_mi355x.model import RequestOptions
+    return RequestOptions(stop=spec)
+
+
 def _free_run(model, ids, pix, n):
     return model.generate(inputs=ids, images=pix, do_sample=False, max_new_tokens=n, eos_token_id=-1)[0, ids.shape[1]:].tolist()
 
@@ -59,7 +64,7 @@ def test_chained_steps_produce_nothing_past_an_eos(cuda):
     ids, pix = _request(cfg, cuda, torch.bfloat16)
     free = _free_run(model, ids, pix, 24)
     k = _first_new(free)
-    cache = model._prefill_request(ids, pix, None, None, stop=([free[k]], []))
+    cache = model._prefill_request(ids, pix, None, _stop(([free[k]], [])))
     seq = cache.seqs[0]
     try:
         assert not _stopped(seq)
@@ -90,7 +95,7 @@ def test_keyword_ids_rule_and_first_pick(cuda):
     k = _first_new(free, start=4)
     # two keywords: one that never occurs, one = the three ids ending at position k
     kw = [[free[k], free[k]], free[k - 2:k + 1]]
-    cache = model._prefill_request(ids, pix, None, None, stop=([], kw))
+    cache = model._prefill_request(ids, pix, None, _stop(([], kw)))
     try:
         check(lib.lmx_decode(model._h, cache.seqs[0], -1, 23, None, 1, stream_handle()), "decode")
         assert _read(model, cache.seqs[0]) == free[:k + 1]
@@ -98,7 +103,7 @@ def test_keyword_ids_rule_and_first_pick(cuda):
     finally:
         cache.close()
     # the prefill's own pick (token 1) is tested too: an EOS equal to it stops the sequence before any decode step
-    cache = model._prefill_request(ids, pix, None, None, stop=([free[0]], []))
+    cache = model._prefill_request(ids, pix, None, _stop(([free[0]], [])))
     try:
         check(lib.lmx_decode(model._h, cache.seqs[0], -1, 8, None, 1, stream_handle()), "decode")
         assert _read(model, cache.seqs[0]) == free[:1]
@@ -112,7 +117,7 @@ def test_decode_batch_reports_minus_one_for_a_stopped_member(cuda):
     reqs = [_request(cfg, cuda, torch.bfloat16, length=20 + 4 * i, seed=10 + i) for i in range(3)]
     free = [_free_run(model, i, p, 16) for i, p in reqs]
     k = _first_new(free[1])
-    caches = [model._prefill_request(i, p, None, None, stop=(([free[1][k]], []) if j == 1 else None)) for j, (i, p) in enumerate(reqs)]
+    caches = [model._prefill_request(i, p, None, _stop(([free[1][k]], []) if j == 1 else None)) for j, (i, p) in enumerate(reqs)]
     batch = DecodeBatch(model, 4)
     try:
         steps = batch.step([c.seqs[0] for c in caches], None, 15, True)          # ids[step][member], token 1 came from the prefill
@@ -136,7 +141,7 @@ def test_lone_batch_member_reports_minus_one_after_its_stop(cuda):
     ids, pix = _request(cfg, cuda, torch.bfloat16, length=22, seed=31)
     free = _free_run(model, ids, pix, 16)
     k = _first_new(free)
-    cache = model._prefill_request(ids, pix, None, None, stop=([free[k]], []))
+    cache = model._prefill_request(ids, pix, None, _stop(([free[k]], [])))
     batch = DecodeBatch(model, 4)
     try:
         len0 = lib.lmx_seq_length(cache.seqs[0])
@@ -217,7 +222,7 @@ def test_host_length_follows_the_device_after_a_stop_with_run_ahead(cuda):
     ids, pix = _request(cfg, cuda, torch.bfloat16)
     free = _free_run(model, ids, pix, 24)
     k = _first_new(free)
-    cache = model._prefill_request(ids, pix, None, None, stop=([free[k]], []))
+    cache = model._prefill_request(ids, pix, None, _stop(([free[k]], [])))
     seq = cache.seqs[0]
     try:
         n_prompt = lib.lmx_seq_length(seq)

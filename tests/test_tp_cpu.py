@@ -180,7 +180,7 @@ def _symmetric_worker(rank, world, port, out_path):
     class Model:
         device = torch.device("cpu")
         def __init__(self, bad_prepare, bad_run): self.bad_prepare, self.bad_run, self.ran, self.made = bad_prepare, bad_run, [], []
-        def _prepare_request(self, ids, images, attention_mask, sampling, stop=None):
+        def _prepare_request(self, ids, images, attention_mask, opts=None):
             tag = int(ids[0, 0])
             if tag in self.bad_prepare:
                 raise MemoryError(f"rank {rank} cannot allocate request {tag}")
@@ -223,9 +223,9 @@ def _symmetric_worker(rank, world, port, out_path):
             if self.bad_encode == "collective": raise RuntimeError(f"rank {rank}: tower all-gather failed")
             return [None if im is None else ("feats", int(im.shape[0])) for im in st["images"]]
         def clear_image_cache(self): self.cleared += 1
-        def _prepare_request(self, ids, images, attention_mask, sampling, stop=None, feats=None):
+        def _prepare_request(self, ids, images, attention_mask, opts=None, feats=None):
             self.got.append(feats)
-            return super()._prepare_request(ids, images, attention_mask, sampling, stop)
+            return super()._prepare_request(ids, images, attention_mask, opts)
     img = lambda k: torch.zeros(k, 3, 4, 4)
     reqs_i = [dict(r, images=im) for r, im in zip(reqs, (img(1), img(2) if rank == 0 else None, img(1)))]
     m = TPModel(False)
