@@ -266,11 +266,13 @@ int lmx_seq_read_tokens(lmx_seq* s, int64_t* host_out, int32_t max_n, int32_t* n
  * bench.py derives its `roofline` objects from this. */
 int lmx_profile_enable(lmx_model* m, int32_t on);
 int lmx_profile_read(lmx_model* m, char* names_buf, int32_t names_cap, double* ms, int64_t* counts, int32_t max_n, int32_t* n_out);
-/* Options of a live model (defaults come from the environment at lmx_create: LMX_FUSE_ROPE, LMX_VIS_PACK, LMX_DECODE_SPLITQ; all default 1).  Every one selects
+/* Options of a live model (defaults come from the environment at lmx_create: LMX_FUSE_ROPE, LMX_VIS_PACK, LMX_DECODE_SPLITQ, LMX_DECODE_ROT; all default 1).  Every one selects
  * between two launch forms with bit-identical results — the switch exists for A/B timing and for the tests that prove the identity:
  *   "fuse_rope"     RoPE + KV-cache append in the prefill's q|k|v GEMM epilogue (HF5:models/llama/modeling_llama.py:130-160,243-281) vs. a rope_kv launch
  *   "vis_pack"      CLIP K / V^T pack in the tower's q|k|v GEMM epilogue (HF5:models/clip/modeling_clip.py:295-340) vs. a pack launch
  *   "decode_splitq" decode step of 16-bit models as q launch + (k|v projection with the attention workgroups) launch vs. q|k|v launch + attention launch
+ *   "decode_rot"    16-bit models: down_proj, the split-q launch's k|v projection and lm_head of a batch-1 decode step stream rotated copies of their weights
+ *                   (made at lmx_finalize_weights, or here when the model was created with LMX_DECODE_ROT=0 and so without them) vs. the plain weights
  * Unknown keys are an error.  Not to be flipped while requests are in flight on other threads. */
 int lmx_model_set_option(lmx_model* m, const char* key, int32_t value);
 
@@ -281,6 +283,15 @@ int lmx_op_gemm(int32_t dtype, const void* x, const void* w, void* c, const void
                 int32_t M, int32_t N, int32_t K, int32_t ldx, int32_t ldw, int32_t ldc, int32_t ldr, int32_t act, int32_t variant, void* stream);
 int lmx_op_gemv(int32_t dtype, const void* x, const void* w, void* c, const void* bias, const void* residual, const void* norm_w, float eps,
                 int32_t MB, int32_t N, int32_t K, int32_t ldx, int32_t ldw, int32_t ldc, int32_t ldr, int32_t act, void* stream);
+/* Rotated decode copy of a 16-bit [N, K] weight and the single-row linear on it: same bits as lmx_op_gemv(MB = 1) on w, another walk over memory.
+ * w_rot holds N rows of lmx_op_gemv_rot_pitch(K) elements (whole 1-KiB load rounds, zero past K).  rows_per_wave = lmx_op_gemv_rot_rows(N, K, norm given, act):
+ * what the single-row launch gives that shape; row n belongs to wave slot s = n / rows_per_wave, and its physical round p holds logical round
+ * (p - (s * rot) % NR + NR) % NR, NR = pitch / 512.  lmx_op_gemv_rot is an error for shapes the hand-counted 16-bit stream does not take. */
+int32_t lmx_op_gemv_rot_pitch(int32_t K);
+int32_t lmx_op_gemv_rot_rows(int32_t N, int32_t K, int32_t has_norm, int32_t act);
+int lmx_op_gemv_rot_pack(int32_t dtype, const void* w, int32_t ldw, void* w_rot, int32_t N, int32_t K, int32_t rows_per_wave, int32_t rot, int32_t act, void* stream);
+int lmx_op_gemv_rot(int32_t dtype, const void* x, const void* w_rot, void* c, const void* bias, const void* residual, const void* norm_w, float eps,
+                    int32_t N, int32_t K, int32_t act, int32_t rot, void* stream);
 int lmx_op_rmsnorm(int32_t dtype, const void* x, const void* w, void* y, int32_t rows, int32_t H, float eps, void* stream);
 int lmx_op_layernorm(int32_t dtype, const void* x, const void* w, const void* b, void* y, int32_t rows, int32_t H, float eps, void* stream);
 int lmx_op_rope_kv(int32_t dtype, int32_t head_dim, void* qkv, void* kcache, void* vtcache, const float* cos_sin_dev, int32_t pos0,
@@ -317,6 +328,10 @@ int lmx_op_decode_attn_step(int32_t dtype, int32_t head_dim, void* qkv, void* kc
 int lmx_op_decode_kv_attn(int32_t dtype, int32_t head_dim, void* qkv, const void* x, const void* w_kv, const void* norm_w, float eps, int32_t K, int32_t ldw,
                           void* kcache, void* vtcache, const float* cos_sin_dev, int32_t pos, int32_t n_heads, int32_t n_kv_heads, int32_t s_max, float scale,
                           void* ws_dev, int32_t* counters_dev, void* granules_dev, uint32_t tag, void* out, void* timeline_dev, void* stream);
+/* lmx_op_decode_kv_attn on the rotated copy of the k | v rows (lmx_op_gemv_rot_pack with rows_per_wave = 2 and step `rot`): bit-identical effects */
+int lmx_op_decode_kv_attn_rot(int32_t dtype, int32_t head_dim, void* qkv, const void* x, const void* w_kv_rot, const void* norm_w, float eps, int32_t K, int32_t rot,
+                              void* kcache, void* vtcache, const float* cos_sin_dev, int32_t pos, int32_t n_heads, int32_t n_kv_heads, int32_t s_max, float scale,
+                              void* ws_dev, int32_t* counters_dev, void* granules_dev, uint32_t tag, void* out, void* timeline_dev, void* stream);
 /* the decode BATCH's attention launch (continuous batching; what Model::decode_batch issues per layer): sequence z of n_seq has its own caches
  * kcaches[z] / vtcaches[z] (this layer's [n_kv_heads][s_max][D] rows and [n_kv_heads][D][s_max] columns) and its own device position word pos_devs[z]
  * (keys already cached; the new key / value of row z of `qkv` are appended there); rows of `qkv` / `out` by element stride.  16-bit models with

@@ -472,6 +472,11 @@ int lmx_model_set_option(lmx_model* m, const char* key, int32_t value) {
     if (k == "fuse_rope") m->impl.opt_fuse_rope = value != 0;
     else if (k == "vis_pack") m->impl.opt_vis_pack = value != 0;
     else if (k == "decode_splitq") m->impl.opt_splitq = value != 0;
+    else if (k == "decode_rot") {                  // switched on behind a model built without the copies (LMX_DECODE_ROT=0): they are made now
+        LMX_REQUIRE(value == 0 || m->impl.cfg.dtype != kF32, "decode_rot: 16-bit models only");
+        if (value) m->impl.ensure_rot_weights(nullptr);
+        m->impl.opt_rot = value != 0;
+    }
     else if (k == "debug_splitq_timeout") m->impl.debug_splitq_timeout = value;
     else throw Error{"lmx_model_set_option: unknown option '" + k + "'"};
     LMX_API_END
@@ -543,6 +548,26 @@ int lmx_op_gemv(int32_t dtype, const void* x, const void* w, void* c, const void
                 int32_t MB, int32_t N, int32_t K, int32_t ldx, int32_t ldw, int32_t ldc, int32_t ldr, int32_t act, void* stream) {
     LMX_API_BEGIN
     launch_gemv(dtype, GemvArgs{x, w, c, bias, residual, norm_w, eps, N, K, ldx, ldw, ldc, ldr, act}, MB, S(stream));
+    LMX_API_END
+}
+// rotated decode copy of a weight (kernels.h: gemv_rot_pitch) and the single-row linear on it: bit-identical to lmx_op_gemv(MB = 1) on the plain weight
+int32_t lmx_op_gemv_rot_pitch(int32_t K) { return K > 0 ? gemv_rot_pitch(K) : 0; }
+int32_t lmx_op_gemv_rot_rows(int32_t N, int32_t K, int32_t has_norm, int32_t act) {
+    GemvArgs g{}; g.N = N; g.K = K; g.act = act; g.norm_w = has_norm ? &g : nullptr;
+    return gemv2_rows_per_wave(g);
+}
+int lmx_op_gemv_rot_pack(int32_t dtype, const void* w, int32_t ldw, void* w_rot, int32_t N, int32_t K, int32_t rows_per_wave, int32_t rot, int32_t act, void* stream) {
+    LMX_API_BEGIN
+    launch_gemv_rot_pack(dtype, w, ldw, w_rot, N, K, rows_per_wave, rot, act == kActSiluMul, S(stream));
+    LMX_API_END
+}
+int lmx_op_gemv_rot(int32_t dtype, const void* x, const void* w_rot, void* c, const void* bias, const void* residual, const void* norm_w, float eps,
+                    int32_t N, int32_t K, int32_t act, int32_t rot, void* stream) {
+    LMX_API_BEGIN
+    LMX_REQUIRE(rot > 0, "gemv_rot: the rotation step of the copy (>= 1)");
+    GemvArgs g{x, w_rot, c, bias, residual, norm_w, eps, N, K, K, gemv_rot_pitch(K), N, N, act};
+    g.rot = rot;
+    launch_gemv(dtype, g, 1, S(stream));
     LMX_API_END
 }
 int lmx_op_rmsnorm(int32_t dtype, const void* x, const void* w, void* y, int32_t rows, int32_t H, float eps, void* stream) {
@@ -630,18 +655,35 @@ int lmx_op_decode_attn_step(int32_t dtype, int32_t head_dim, void* qkv, void* kc
     launch_decode_attn_step(dtype, head_dim, a, S(stream));
     LMX_API_END
 }
-int lmx_op_decode_kv_attn(int32_t dtype, int32_t head_dim, void* qkv, const void* x, const void* w_kv, const void* norm_w, float eps, int32_t K, int32_t ldw,
-                          void* kcache, void* vtcache, const float* cos_sin_dev, int32_t pos, int32_t n_heads, int32_t n_kv_heads, int32_t s_max, float scale,
-                          void* ws_dev, int32_t* counters_dev, void* granules_dev, uint32_t tag, void* out, void* timeline_dev, void* stream) {
-    LMX_API_BEGIN
+static void decode_kv_attn_op(int32_t dtype, int32_t head_dim, void* qkv, const void* x, const void* w_kv, const void* norm_w, float eps, int32_t K, int32_t ldw, int32_t rot,
+                             void* kcache, void* vtcache, const float* cos_sin_dev, int32_t pos, int32_t n_heads, int32_t n_kv_heads, int32_t s_max, float scale,
+                             void* ws_dev, int32_t* counters_dev, void* granules_dev, uint32_t tag, void* out, void* timeline_dev, void* stream) {
     LMX_REQUIRE(qkv && x && w_kv && granules_dev && out, "null argument");
     DecAttnArgs a{};
     a.qkv = qkv; a.attn = out; a.kc = kcache; a.vt = vtcache; a.rope = cos_sin_dev; a.aws = static_cast<float*>(ws_dev); a.cnt = counters_dev;
     a.pos = pos; a.n_split = pos / 128 + 1; a.nh = n_heads; a.nkv = n_kv_heads; a.s_max = s_max; a.scale = scale;
     a.kv_gran = static_cast<unsigned long long*>(granules_dev); a.tag = tag; a.ts = static_cast<unsigned long long*>(timeline_dev);
     const int kv_n = 2 * n_kv_heads * head_dim;
-    const GemvArgs g{x, w_kv, nullptr, nullptr, nullptr, norm_w, eps, kv_n, K, K, ldw, kv_n, 0, kActNone};
+    GemvArgs g{x, w_kv, nullptr, nullptr, nullptr, norm_w, eps, kv_n, K, K, ldw, kv_n, 0, kActNone};
+    g.rot = rot;
     launch_decode_kv_attn(dtype, head_dim, a, g, S(stream));
+}
+int lmx_op_decode_kv_attn(int32_t dtype, int32_t head_dim, void* qkv, const void* x, const void* w_kv, const void* norm_w, float eps, int32_t K, int32_t ldw,
+                          void* kcache, void* vtcache, const float* cos_sin_dev, int32_t pos, int32_t n_heads, int32_t n_kv_heads, int32_t s_max, float scale,
+                          void* ws_dev, int32_t* counters_dev, void* granules_dev, uint32_t tag, void* out, void* timeline_dev, void* stream) {
+    LMX_API_BEGIN
+    decode_kv_attn_op(dtype, head_dim, qkv, x, w_kv, norm_w, eps, K, ldw, 0, kcache, vtcache, cos_sin_dev, pos, n_heads, n_kv_heads, s_max, scale, ws_dev, counters_dev,
+                      granules_dev, tag, out, timeline_dev, stream);
+    LMX_API_END
+}
+// the same launch on the rotated copy of the k | v rows (lmx_op_gemv_rot_pack with rows_per_wave = 2, step `rot`)
+int lmx_op_decode_kv_attn_rot(int32_t dtype, int32_t head_dim, void* qkv, const void* x, const void* w_kv_rot, const void* norm_w, float eps, int32_t K, int32_t rot,
+                              void* kcache, void* vtcache, const float* cos_sin_dev, int32_t pos, int32_t n_heads, int32_t n_kv_heads, int32_t s_max, float scale,
+                              void* ws_dev, int32_t* counters_dev, void* granules_dev, uint32_t tag, void* out, void* timeline_dev, void* stream) {
+    LMX_API_BEGIN
+    LMX_REQUIRE(rot > 0 && K > 0, "decode_kv_attn_rot: the rotation step of the copy (>= 1)");
+    decode_kv_attn_op(dtype, head_dim, qkv, x, w_kv_rot, norm_w, eps, K, gemv_rot_pitch(K), rot, kcache, vtcache, cos_sin_dev, pos, n_heads, n_kv_heads, s_max, scale, ws_dev,
+                      counters_dev, granules_dev, tag, out, timeline_dev, stream);
     LMX_API_END
 }
 int lmx_op_decode_attn_batch(int32_t dtype, int32_t head_dim, const void* qkv, int32_t qkv_stride, void* const* kcaches, void* const* vtcaches,

@@ -291,11 +291,12 @@ __global__ __launch_bounds__(256) void decode_attn_step_kernel(DecAttnArgs a) {
 }
 
 // attention workgroups [0, n_attn) + the k|v projection's workgroups behind them (R = 2 rows per wave, P = 4 rounds in flight: the q|k|v shape's setting)
-template <typename T, int D, int NX>
+// ROT: g.W is the rotated decode copy of the k|v rows (gemv2.h), laid out for R = 2
+template <typename T, int D, int NX, bool ROT>
 __global__ __launch_bounds__(256) void decode_kv_attn_kernel(DecAttnArgs a, GemvArgs g, int n_attn) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if ((int)blockIdx.x < n_attn) dec_attn_chunk<T, D, true>(a, (int)blockIdx.x, smem);
-    else gemv2_body<T, 2, 4, NX, true>(g, (int)blockIdx.x - n_attn, smem, a.kv_gran, a.pub_tag ? a.pub_tag : a.tag, a.ts);
+    else gemv2_body<T, 2, 4, NX, true, ROT>(g, (int)blockIdx.x - n_attn, smem, a.kv_gran, a.pub_tag ? a.pub_tag : a.tag, a.ts);
 }
 
 void check_dec_attn(int D, const DecAttnArgs& a, const char* who) {      // (the dtype: the launcher's dispatch_dtype16, which runs first)
@@ -334,7 +335,8 @@ int decode_kv_attn_resident_slots(int dtype, int D, int K) {
     dispatch_dtype16(dtype, "decode_kv_attn_resident_slots", [&](auto t) {
         dispatch_head_dim(D, "decode_kv_attn_resident_slots", [&](auto d) {
             constexpr int DD = decltype(d)::value;
-            const auto kern = K <= 4096 ? decode_kv_attn_kernel<LMX_T(t), DD, 2> : decode_kv_attn_kernel<LMX_T(t), DD, 4>;
+            // (the plain and the rotated form take the same registers and LDS: one answer for both)
+            const auto kern = K <= 4096 ? decode_kv_attn_kernel<LMX_T(t), DD, 2, false> : decode_kv_attn_kernel<LMX_T(t), DD, 4, false>;
             LMX_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, smem));
         });
     });
@@ -346,6 +348,7 @@ void launch_decode_kv_attn(int dtype, int D, const DecAttnArgs& a, const GemvArg
         check_dec_attn(D, a, "decode_kv_attn");
         LMX_REQUIRE(decode_kv_attn_applies(dtype, D, g), "decode_kv_attn: the k|v projection must be a plain 16-bit linear the hand-counted stream takes, K <= 8192");
         LMX_REQUIRE(g.N == 2 * a.nkv * D && a.kv_gran && a.tag != 0, "decode_kv_attn: the projection's rows are k | v of every kv head; granules and a non-zero tag");
+        LMX_REQUIRE(g.rot == 0 || (g.rot > 0 && g.ldw == gemv_rot_pitch(g.K)), "decode_kv_attn: a rotated weight copy has ldw = gemv_rot_pitch(K)");
         const size_t smem_g = gemv2_smem_bytes(g.K, 2), smem_a = dec_attn_smem_bytes(D);
         const size_t smem = smem_g > smem_a ? smem_g : smem_a;
         const int n_attn = a.nh * a.n_split;
@@ -354,7 +357,8 @@ void launch_decode_kv_attn(int dtype, int D, const DecAttnArgs& a, const GemvArg
         const dim3 grid((unsigned)(n_attn + cdiv(g.N, 8)));
         dispatch_head_dim(D, "decode_kv_attn", [&](auto d) {
             constexpr int DD = decltype(d)::value;
-            const auto kern = g.K <= 4096 ? decode_kv_attn_kernel<LMX_T(t), DD, 2> : decode_kv_attn_kernel<LMX_T(t), DD, 4>;
+            const auto kern = g.rot ? (g.K <= 4096 ? decode_kv_attn_kernel<LMX_T(t), DD, 2, true> : decode_kv_attn_kernel<LMX_T(t), DD, 4, true>)
+                                    : (g.K <= 4096 ? decode_kv_attn_kernel<LMX_T(t), DD, 2, false> : decode_kv_attn_kernel<LMX_T(t), DD, 4, false>);
             LMX_LAUNCH(kern, grid, dim3(256), smem, st, a, g, n_attn);
         });
     });

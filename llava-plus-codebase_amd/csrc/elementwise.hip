@@ -502,6 +502,32 @@ void launch_interleave_half(int dtype, const void* src, void* dst, int I, int K,
     LMX_CHECK_HIP(hipGetLastError());
 }
 
+// Rotated decode copy of a 16-bit [N, K] weight (kernels.h: gemv_rot_pitch; read by gemv2_body's ROT form): one workgroup per row, 16-byte chunks.  Physical round
+// p of the row holds logical round (p - krot + NR) % NR, krot = (s * rot) % NR, s = the wave slot gemv2_body gives the row (n / R; through the gate|up pairing
+// with SiLU.mul); chunks past K are zero.
+__global__ __launch_bounds__(256) void gemv_rot_pack_kernel(const uint4* __restrict__ src, int ld8, uint4* __restrict__ dst, int KC, int NR, int R, int rot, int silu) {
+    const int n = blockIdx.x;
+    const int slot = silu ? 2 * (32 * (n >> 6) + (n & 31)) + ((n >> 5) & 1) : n;
+    const int krot = (int)((unsigned)((slot / R) * rot) % (unsigned)NR);
+    const uint4* s = src + (size_t)n * ld8;
+    uint4* d = dst + (size_t)n * NR * 64;
+    for (int pc = threadIdx.x; pc < NR * 64; pc += 256) {
+        int jl = (pc >> 6) - krot;
+        if (jl < 0) jl += NR;
+        const int lc = jl * 64 + (pc & 63);
+        d[pc] = lc < KC ? s[lc] : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+void launch_gemv_rot_pack(int dtype, const void* W, int ldw, void* dst, int N, int K, int R, int rot, bool silu, hipStream_t st) {
+    LMX_REQUIRE(dtype == kBF16 || dtype == kF16, "gemv_rot_pack: 16-bit weights");
+    LMX_REQUIRE(W && dst && N > 0 && K > 0 && K % 8 == 0 && ldw >= K && ldw % 8 == 0 && reinterpret_cast<uintptr_t>(W) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0,
+                "gemv_rot_pack: 16-byte aligned rows of a [N, K] weight");
+    LMX_REQUIRE((R == 1 || R == 2) && rot >= 1 && rot <= 64 && (!silu || (N % 64 == 0 && R == 2)), "gemv_rot_pack: R in {1, 2}, step in 1..64, SiLU.mul rows in pairs of 32");
+    hipLaunchKernelGGL(gemv_rot_pack_kernel, dim3(N), dim3(256), 0, st, static_cast<const uint4*>(W), ldw / 8, static_cast<uint4*>(dst), K / 8, gemv_rot_pitch(K) / 512, R, rot, silu ? 1 : 0);
+    LMX_CHECK_HIP(hipGetLastError());
+}
+
 __global__ void set_state_kernel(int* len_ptr, int len, int64_t* tok_ptr, int64_t tok, int set_tok, int* nout_ptr, int set_nout) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         if (len >= 0) *len_ptr = len;

@@ -46,6 +46,8 @@ Model::Model(const lmx_config& c) : cfg(c) {
     { const char* e = getenv("LMX_FUSE_ROPE"); if (e) opt_fuse_rope = atoi(e) != 0; }
     { const char* e = getenv("LMX_VIS_PACK"); if (e) opt_vis_pack = atoi(e) != 0; }
     { const char* e = getenv("LMX_DECODE_SPLITQ"); if (e) opt_splitq = atoi(e) != 0; }
+    { const char* e = getenv("LMX_DECODE_ROT"); if (e) opt_rot = atoi(e) != 0; }
+    if (c.dtype == kF32) opt_rot = false;                     // the hand-counted stream is the 16-bit models'
     { const char* e = getenv("LMX_TP_OVERLAP"); if (e) { tp_overlap = atoi(e) != 0; tp_overlap_force = atoi(e) == 2; } }
     H = c.hidden_size; D = c.head_dim; V = c.vocab_size; Vr = V; L = c.n_layers;
     LMX_REQUIRE(D == 64 || D == 128, "head_dim must be 64 or 128");
@@ -166,6 +168,7 @@ void Model::load_weight(const std::string& name, const void* src, int dtype, int
             if (!lm_head) lm_head = alloc_weight((size_t)V_l * H * es);
             LMX_CHECK_HIP(hipMemcpyAsync(lm_head, static_cast<const char*>(src) + (size_t)v_off * H * es, (size_t)V_l * H * es, hipMemcpyDeviceToDevice, st));
         }
+        pack_rot_head(st);                                    // a reload behind finalize(): the rotated copy follows its source
     }
     else if (starts_with(name, "model.layers.")) {
         const size_t p0 = strlen("model.layers.");
@@ -181,13 +184,13 @@ void Model::load_weight(const std::string& name, const void* src, int dtype, int
             w.wgu = alloc_weight((size_t)2 * I_l * H * es, I_l != I_sh);
             w.wd = alloc_weight((size_t)H * I_l * es, I_l != I_sh);
         }
-        if (sub == "self_attn.q_proj.weight") { expect({(int64_t)nh * D, H}); copy_block(w.wqkv, H, 0, src, H, r * nh_l * D, 0, nh_l * D, H, es, st); }
-        else if (sub == "self_attn.k_proj.weight") { expect({(int64_t)nkv * D, H}); copy_block(w.wqkv, H, nh_l * D, src, H, r * nkv_l * D, 0, nkv_l * D, H, es, st); }
-        else if (sub == "self_attn.v_proj.weight") { expect({(int64_t)nkv * D, H}); copy_block(w.wqkv, H, (nh_l + nkv_l) * D, src, H, r * nkv_l * D, 0, nkv_l * D, H, es, st); }
-        else if (sub == "self_attn.o_proj.weight") { expect({H, (int64_t)nh * D}); copy_block(w.wo, nh_l * D, 0, src, nh * D, 0, r * nh_l * D, H, nh_l * D, es, st); }
+        if (sub == "self_attn.q_proj.weight") { expect({(int64_t)nh * D, H}); copy_block(w.wqkv, H, 0, src, H, r * nh_l * D, 0, nh_l * D, H, es, st); pack_rot_layer(w, kRotQ, st); }
+        else if (sub == "self_attn.k_proj.weight") { expect({(int64_t)nkv * D, H}); copy_block(w.wqkv, H, nh_l * D, src, H, r * nkv_l * D, 0, nkv_l * D, H, es, st); pack_rot_layer(w, kRotKv, st); }
+        else if (sub == "self_attn.v_proj.weight") { expect({(int64_t)nkv * D, H}); copy_block(w.wqkv, H, (nh_l + nkv_l) * D, src, H, r * nkv_l * D, 0, nkv_l * D, H, es, st); pack_rot_layer(w, kRotKv, st); }
+        else if (sub == "self_attn.o_proj.weight") { expect({H, (int64_t)nh * D}); copy_block(w.wo, nh_l * D, 0, src, nh * D, 0, r * nh_l * D, H, nh_l * D, es, st); pack_rot_layer(w, kRotO, st); }
         else if (sub == "mlp.gate_proj.weight") { expect({I, H}); launch_interleave_half(cfg.dtype, static_cast<const char*>(src) + (size_t)r * I_sh * H * es, w.wgu, I_sh, H, 0, st); }
         else if (sub == "mlp.up_proj.weight") { expect({I, H}); launch_interleave_half(cfg.dtype, static_cast<const char*>(src) + (size_t)r * I_sh * H * es, w.wgu, I_sh, H, 1, st); }
-        else if (sub == "mlp.down_proj.weight") { expect({H, I}); copy_block(w.wd, I_l, 0, src, I, 0, r * I_sh, H, I_sh, es, st); }
+        else if (sub == "mlp.down_proj.weight") { expect({H, I}); copy_block(w.wd, I_l, 0, src, I, 0, r * I_sh, H, I_sh, es, st); pack_rot_layer(w, kRotDown, st); }
         else if (sub == "input_layernorm.weight") { expect({H}); plain(w.ln1); }
         else if (sub == "post_attention_layernorm.weight") { expect({H}); plain(w.ln2); }
         else if (sub == "self_attn.rotary_emb.inv_freq") { return; }   // buffer in old checkpoints; recomputed
@@ -291,6 +294,48 @@ void Model::finalize() {
     }
     if (!rope) missing += "<rope table: call lmx_set_rope_table> ";
     if (!missing.empty()) throw Error{"missing tensors: " + missing};
+    if (opt_rot) ensure_rot_weights(nullptr);
+}
+
+// ---- rotated decode copies (engine.h) ---------------------------------------------------------------------------------
+// Each copy is laid out for the rows-per-wave of the launch that reads it, so the shapes here are decode_step_launch's (N, K, norm, activation).
+void Model::pack_rot(void*& dst, const void* W, const GemvArgs& launch, int R, hipStream_t st) {
+    if (!dst) dst = alloc_weight((size_t)launch.N * gemv_rot_pitch(launch.K) * es);
+    launch_gemv_rot_pack(cfg.dtype, W, launch.K, dst, launch.N, launch.K, R, kRotStep, false, st);
+}
+static GemvArgs rot_shape(int N, int K, const void* norm_w) { GemvArgs g{}; g.N = N; g.K = K; g.norm_w = norm_w; return g; }
+
+void Model::pack_rot_layer(DecLayerW& w, int which, hipStream_t st) {
+    which &= rot_live;
+    const int q_n = nh_l * D, kv_n = 2 * nkv_l * D;
+    if ((which & kRotDown) && w.wd) { const GemvArgs g = rot_shape(H, I_l, nullptr); pack_rot(w.rot_d, w.wd, g, gemv2_rows_per_wave(g), st); }
+    if ((which & kRotO) && w.wo) { const GemvArgs g = rot_shape(H, q_n, nullptr); pack_rot(w.rot_o, w.wo, g, gemv2_rows_per_wave(g), st); }
+    if ((which & kRotQ) && w.wqkv) { const GemvArgs g = rot_shape(q_n, H, w.wqkv);      /* non-null norm_w: the launch fuses the RMSNorm, which decides its rows per wave */ pack_rot(w.rot_q, w.wqkv, g, gemv2_rows_per_wave(g), st); }
+    // decode_kv_attn_kernel's projection part: 2 rows per wave
+    if ((which & kRotKv) && w.wqkv) pack_rot(w.rot_kv, static_cast<const char*>(w.wqkv) + (size_t)q_n * H * es, rot_shape(kv_n, H, nullptr), 2, st);
+}
+void Model::pack_rot_head(hipStream_t st) {
+    if (!(rot_live & kRotHead) || !lm_head) return;
+    const GemvArgs g = rot_shape(V_l, H, lm_head);      // (non-null norm_w: the launch fuses the final norm)
+    pack_rot(rot_lm_head, lm_head, g, gemv2_rows_per_wave(g), st);
+}
+
+void Model::ensure_rot_weights(hipStream_t st) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (cfg.dtype == kF32) return;
+    LMX_CHECK_HIP(hipDeviceSynchronize());                   // the sources may have been written on any stream
+    // a copy only where the launch that would read it exists: the hand-counted stream over the packed pitch (32-bit row offsets); q and k|v: the split-q step
+    auto fits = [&](int N, int K) { GemvArgs g = rot_shape(N, K, nullptr); g.ldw = gemv_rot_pitch(K); return gemv2_applies(cfg.dtype, g); };
+    const int q_n = nh_l * D, kv_n = 2 * nkv_l * D;
+    GemvArgs gkv = rot_shape(kv_n, H, nullptr); gkv.ldw = gemv_rot_pitch(H);
+    const bool splitq_ok = decode_kv_attn_applies(cfg.dtype, D, gkv) && s_max % 128 == 0 && s_max / 128 <= 32;
+    const int live = (fits(H, I_l) ? kRotDown : 0) | (fits(H, q_n) ? kRotO : 0) | (fits(V_l, H) ? kRotHead : 0) | (splitq_ok ? kRotKv : 0) | (splitq_ok && fits(q_n, H) ? kRotQ : 0);
+    const int fresh = rot_set & live & ~rot_live;            // nothing to do on a second call
+    rot_live |= fresh;
+    if (!fresh) return;
+    for (auto& w : dec) pack_rot_layer(w, fresh, st);
+    if (fresh & kRotHead) pack_rot_head(st);
+    LMX_CHECK_HIP(hipStreamSynchronize(st));
 }
 
 void Model::set_rope(const float* host, int n_pos) {
@@ -717,7 +762,7 @@ void Model::prefill_head(Seq* s, const void* h_row, void* dst, bool pick, hipStr
     const int dt = cfg.dtype;
     // vocabulary-parallel head: this rank computes columns [v_off, v_off + V_l) of a zeroed row, the sum over ranks completes it
     if (V_l != V) LMX_CHECK_HIP(hipMemsetAsync(dst, 0, (size_t)V * es, st));
-    { LMX_PROF_K("prefill.gemv.lm_head"); launch_gemv(dt, GemvArgs{h_row, lm_head, static_cast<char*>(dst) + (size_t)v_off * es, nullptr, nullptr, final_norm, cfg.rms_eps, V_l, H, H, H, V, 0, kActNone}, 1, st); }
+    { LMX_PROF_K("prefill.gemv.lm_head"); launch_gemv(dt, rot_args(GemvArgs{h_row, lm_head, static_cast<char*>(dst) + (size_t)v_off * es, nullptr, nullptr, final_norm, cfg.rms_eps, V_l, H, H, H, V, 0, kActNone}, rot_lm_head, kRotStep), 1, st); }
     gather_logits(dst, 1, st);
     if (!pick) return;
     // with logits processors: the ruled pick (history = the prompt ids + whatever the log holds: nothing, for a request's first token)
@@ -851,11 +896,11 @@ void Model::decode_step_launch(Seq* s, hipStream_t st, int64_t* id_out) {
         // rows [q_n, q_n + kv_n) of the fused q|k|v weight: the k | v projection of the split-q form
         const GemvArgs gkv{s->d_h, static_cast<const char*>(w.wqkv) + (size_t)q_n * H * es, nullptr, nullptr, nullptr, w.ln1, cfg.rms_eps, kv_n, H, H, H, kv_n, 0, kActNone};
         if (attn16 && splitq_allowed() && decode_kv_attn_applies(dt, D, gkv)) {
-            { LMX_PROF_K("decode.gemv.q"); launch_gemv(dt, GemvArgs{s->d_h, w.wqkv, s->d_qkv, nullptr, nullptr, w.ln1, cfg.rms_eps, q_n, H, H, H, q_n, 0, kActNone}, 1, st); }
+            { LMX_PROF_K("decode.gemv.q"); launch_gemv(dt, rot_args(GemvArgs{s->d_h, w.wqkv, s->d_qkv, nullptr, nullptr, w.ln1, cfg.rms_eps, q_n, H, H, H, q_n, 0, kActNone}, w.rot_q, kRotStep), 1, st); }
             a.kv_gran = s->kv_gran.as<unsigned long long>(); a.tag = s->attn_tag;
             if (debug_splitq_timeout.load(std::memory_order_relaxed) > 0 && debug_splitq_timeout.fetch_sub(1) > 0) a.pub_tag = a.tag ^ 0x40000000u;
             s->attn_tag = s->attn_tag >= 0xfffffff0u ? 1u : s->attn_tag + 1;
-            { LMX_PROF_K("decode.kv_attn"); launch_decode_kv_attn(dt, D, a, gkv, st); }
+            { LMX_PROF_K("decode.kv_attn"); launch_decode_kv_attn(dt, D, a, rot_args(gkv, w.rot_kv, kRotStep), st); }
         } else {
             { LMX_PROF_K("decode.gemv.qkv"); launch_gemv(dt, GemvArgs{s->d_h, w.wqkv, s->d_qkv, nullptr, nullptr, w.ln1, cfg.rms_eps, qkv_n, H, H, H, qkv_n, 0, kActNone}, 1, st); }
             LMX_PROF("decode.attn");
@@ -865,14 +910,14 @@ void Model::decode_step_launch(Seq* s, hipStream_t st, int64_t* id_out) {
                 launch_decode_fused(dt, D, fa, st);
             }
         }
-        { LMX_PROF_K("decode.gemv.o"); launch_gemv(dt, GemvArgs{s->d_attn, w.wo, s->d_h, nullptr, lead ? s->d_h : nullptr, nullptr, 0.f, H, nh_l * D, nh_l * D, nh_l * D, H, H, kActNone}, 1, st); }
+        { LMX_PROF_K("decode.gemv.o"); launch_gemv(dt, rot_args(GemvArgs{s->d_attn, w.wo, s->d_h, nullptr, lead ? s->d_h : nullptr, nullptr, 0.f, H, nh_l * D, nh_l * D, nh_l * D, H, H, kActNone}, w.rot_o, kRotStep), 1, st); }
         { LMX_PROF_AR("decode.allreduce"); allreduce(s->d_h, (size_t)H, st); }
         { LMX_PROF_K("decode.gemv.gate_up"); launch_gemv(dt, GemvArgs{s->d_h, w.wgu, s->d_act, nullptr, nullptr, w.ln2, cfg.rms_eps, 2 * I_l, H, H, H, I_l, 0, kActSiluMul}, 1, st); }
-        { LMX_PROF_K("decode.gemv.down"); launch_gemv(dt, GemvArgs{s->d_act, w.wd, s->d_h, nullptr, lead ? s->d_h : nullptr, nullptr, 0.f, H, I_l, I_l, I_l, H, H, kActNone}, 1, st); }
+        { LMX_PROF_K("decode.gemv.down"); launch_gemv(dt, rot_args(GemvArgs{s->d_act, w.wd, s->d_h, nullptr, lead ? s->d_h : nullptr, nullptr, 0.f, H, I_l, I_l, I_l, H, H, kActNone}, w.rot_d, kRotStep), 1, st); }
         allreduce(s->d_h, (size_t)H, st);
     }
     if (V_l != V) LMX_CHECK_HIP(hipMemsetAsync(s->d_logits, 0, (size_t)V * es, st));
-    { LMX_PROF_K("decode.gemv.lm_head"); launch_gemv(dt, GemvArgs{s->d_h, lm_head, static_cast<char*>(s->d_logits) + (size_t)v_off * es, nullptr, nullptr, final_norm, cfg.rms_eps, V_l, H, H, H, V, 0, kActNone}, 1, st); }
+    { LMX_PROF_K("decode.gemv.lm_head"); launch_gemv(dt, rot_args(GemvArgs{s->d_h, lm_head, static_cast<char*>(s->d_logits) + (size_t)v_off * es, nullptr, nullptr, final_norm, cfg.rms_eps, V_l, H, H, H, V, 0, kActNone}, rot_lm_head, kRotStep), 1, st); }
     { ProfScope ps_ag(this, V_l != V ? "decode.allgather.logits" : nullptr, st); gather_logits(s->d_logits, 1, st); }
     {
         LMX_PROF("decode.argmax");      // pick (argmax | draw) + *len += 1 + token log + next token's embedding row -> d_h, one launch

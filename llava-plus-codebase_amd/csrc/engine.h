@@ -48,6 +48,7 @@ struct Carve {
 struct DecLayerW {
     void *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wd = nullptr, *ln1 = nullptr, *ln2 = nullptr;
     void *sw_qkv = nullptr, *sw_o = nullptr, *sw_gu = nullptr, *sw_d = nullptr;   // fragment-order copies for the decode-batch kernel
+    void *rot_d = nullptr, *rot_kv = nullptr, *rot_q = nullptr, *rot_o = nullptr;   // rotated decode copies: wd, the k|v rows and the q rows of wqkv, wo (Model::ensure_rot_weights)
 };
 struct VisLayerW {
     void *wqkv = nullptr, *bqkv = nullptr, *wo = nullptr, *bo = nullptr, *fc1 = nullptr, *b1 = nullptr, *fc2 = nullptr, *b2 = nullptr;
@@ -70,6 +71,25 @@ struct Model {
     std::vector<DevBuf> pool;   // owns every weight allocation
     void* embed = nullptr; void* final_norm = nullptr; void* lm_head = nullptr; void* sw_lm_head = nullptr;
     bool batch_weights_ready = false;
+    // Rotated decode copies (kernels.h: gemv_rot_pitch) of the weights whose batch-1 decode launch gains from waves that start their rows at different rounds
+    // (tools/mb_gemv_rot.py, profiles/gemv_rot_sweep.jsonl): down_proj, the split-q step's k|v and q rows of q|k|v, o_proj and lm_head; gate|up does not gain and
+    // stays plain.  Same bits as the plain weights through gemv2_body's ROT form.  Made at finalize() when the option is on (or when it is switched on later);
+    // load_weight re-packs a copy whose source it has just rewritten.  Every other reader — prefill GEMMs, the decode batch, the three-launch decode form's
+    // q|k|v launch, the fp32 engine, training — keeps the plain tensors.  Steps 1 / 3 / 5 measure alike; 3 is the step of the first experiment.
+    enum : int { kRotDown = 1, kRotKv = 2, kRotHead = 4, kRotQ = 8, kRotO = 16 };
+    static constexpr int kRotStep = 3;
+    static constexpr int rot_set = kRotDown | kRotKv | kRotHead | kRotQ | kRotO;     // linears that get a copy: all but gate|up (profiles/EXPERIMENTS.md)
+    int rot_live = 0;                                              // ... of which this model's shapes take the hand-counted stream: set by ensure_rot_weights
+    void* rot_lm_head = nullptr;
+    void ensure_rot_weights(hipStream_t st);      // makes the copies that do not exist yet (idempotent)
+    void pack_rot(void*& dst, const void* W, const GemvArgs& launch, int R, hipStream_t st);
+    void pack_rot_layer(DecLayerW& w, int which, hipStream_t st);      // (re)packs the copies `which` (kRot* bits) of one layer, as far as they are live
+    void pack_rot_head(hipStream_t st);
+    // the GemvArgs of a decode linear on its rotated copy, when the option is on and the copy exists
+    GemvArgs rot_args(GemvArgs g, const void* packed, int step) const {
+        if (opt_rot && packed) { g.W = packed; g.ldw = gemv_rot_pitch(g.K); g.rot = step; }
+        return g;
+    }
     void ensure_batch_weights(hipStream_t st);      // second, fragment-order copy of the decoder weights (first Batch pays for it)
     std::vector<DecLayerW> dec;
     void *v_cls = nullptr, *v_patch_w = nullptr, *v_pos = nullptr, *v_pre_w = nullptr, *v_pre_b = nullptr;
@@ -164,7 +184,8 @@ struct Model {
     // fuse_rope: RoPE + KV append in the prefill's q|k|v GEMM epilogue (gemm8p.hip qkv_rope_epilogue) instead of a rope_kv launch — bit-identical, faster
     // vis_pack:  CLIP K / V^T pack in the tower's q|k|v GEMM epilogue instead of a pack launch — bit-identical, launch count
     // splitq:    the decode step's q|k|v projection as q-launch + (k|v projection ∥ attention) launch (decode_attn.hip) — bit-identical
-    bool opt_fuse_rope = true, opt_vis_pack = true, opt_splitq = true;
+    // rot:       down_proj, the split-q launch's k|v projection and lm_head of a batch-1 decode step read rotated copies of their weights — bit-identical
+    bool opt_fuse_rope = true, opt_vis_pack = true, opt_splitq = true, opt_rot = true;
     // Sequences in existence (lmx_seq_create .. lmx_seq_destroy).  The split-q launch parks one waiting workgroup per head until its own launch's projection has
     // run; launches of DIFFERENT sequences (request threads on their own streams) may be resident together, so the form is only taken while all sequences'
     // waiters together (live_seqs x heads) fill at most half of the chip's ~1024 workgroup slots — the projection's workgroups then always find a slot

@@ -623,10 +623,10 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
 // gemv2_kernel: the single-row decode linear of 16-bit models with a hand-counted weight stream — body in gemv2.h (shared with the decode step's fused
 // k|v projection + attention launch, decode_attn.hip)
 // ---------------------------------------------------------------------------------------------
-template <typename T, int R, int P, int GEMV2_NX>
+template <typename T, int R, int P, int GEMV2_NX, bool ROT>
 __global__ __launch_bounds__(256) void gemv2_kernel(GemvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    gemv2_body<T, R, P, GEMV2_NX, false>(a, (int)blockIdx.x, smem, nullptr, 0u);
+    gemv2_body<T, R, P, GEMV2_NX, false, ROT>(a, (int)blockIdx.x, smem, nullptr, 0u);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -762,21 +762,26 @@ static void launch_gemv_r(const GemvArgs& a, hipStream_t st) {
     LMX_CHECK_HIP(hipGetLastError());
 }
 
-template <typename T, int R, int P, int NX>
+template <typename T, int R, int P, int NX, bool ROT>
 static void launch_gemv2_rx(const GemvArgs& a, hipStream_t st) {
     const size_t smem = gemv2_smem_bytes(a.K, (int)sizeof(T));
-    auto kern = gemv2_kernel<T, R, P, NX>;
+    auto kern = gemv2_kernel<T, R, P, NX, ROT>;
     static bool attr_set = false;
     if (!attr_set) { LMX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_set = true; }
     LMX_LAUNCH(kern, dim3(cdiv(a.N, 4 * R)), dim3(256), smem, st, a);
     LMX_CHECK_HIP(hipGetLastError());
 }
+template <typename T, int R, int P, bool ROT>
+static void launch_gemv2_k(const GemvArgs& a, hipStream_t st) {
+    if (a.K <= 4096) launch_gemv2_rx<T, R, P, 2, ROT>(a, st);
+    else if (a.K <= 8192) launch_gemv2_rx<T, R, P, 4, ROT>(a, st);
+    else if (a.K <= 12288) launch_gemv2_rx<T, R, P, 6, ROT>(a, st);
+    else launch_gemv2_rx<T, R, P, 8, ROT>(a, st);
+}
 template <typename T, int R, int P>
 static void launch_gemv2_r(const GemvArgs& a, hipStream_t st) {
-    if (a.K <= 4096) launch_gemv2_rx<T, R, P, 2>(a, st);
-    else if (a.K <= 8192) launch_gemv2_rx<T, R, P, 4>(a, st);
-    else if (a.K <= 12288) launch_gemv2_rx<T, R, P, 6>(a, st);
-    else launch_gemv2_rx<T, R, P, 8>(a, st);
+    if (a.rot) launch_gemv2_k<T, R, P, true>(a, st);        // the rotated decode copy of the weight (kernels.h: gemv_rot_pitch)
+    else launch_gemv2_k<T, R, P, false>(a, st);
 }
 
 // does the single-row linear of this shape take the hand-counted stream (gemv2_body)?  16-byte rows, 32-bit row offsets, K <= 16384, an aligned x row.  (launch_gemv
@@ -790,17 +795,27 @@ bool gemv2_applies(int dtype, const GemvArgs& a) {
 // The single-row decode linears of 16-bit models take the hand-counted stream.  (R rows per wave, P rounds in flight) per shape from the in-situ sweep
 // of round 3 (tools/mb_decode.py, LLaVA-1.5-7B, per launch incl. ~1.4 us of event pair; gemv_kernel -> gemv2_kernel): q|k|v 20.5 -> 19.1 us (R 2, P 4),
 // gate|up 30.9 -> 29.5 (2, 4), down 19.9 -> 17.8 (1, 8: K = 11008 keeps 8 KB per wave on the wire), lm_head 45.8 -> 42.2 (2, 4), o_proj 8.7 -> 8.8 (1, 2).
+// The rule in one place: 0 = (2, 4), 1 = (1, 8), 2 = (1, 2).  (The rotated copy of a weight is laid out for the R of its launch: gemv2_rows_per_wave.)
+static int gemv2_rp(const GemvArgs& a) {
+    if (a.act == kActSiluMul) return 0;
+    if (a.K >= 8192) return 1;
+    // small linears (<= 32 M weights): o_proj keeps one row per wave (1024 short-lived workgroups); with the RMSNorm fused — the split-q step's q projection — every
+    // workgroup also normalises the whole input row, so half as many workgroups with two rows per wave win: 8.1 -> 7.5 us (profiles/r05_small_gemv_rp.txt)
+    if ((size_t)a.N * a.K <= ((size_t)1 << 25)) return a.norm_w ? 0 : 2;
+    return 0;
+}
+int gemv2_rows_per_wave(const GemvArgs& a) { return gemv2_rp(a) == 0 ? 2 : 1; }
+
 template <typename T>
 static bool launch_gemv2(const GemvArgs& a, hipStream_t st) {
     if constexpr (sizeof(T) != 2) return false;
     else {
         if (!gemv2_applies(TypeInfo<T>::id, a)) return false;
-        if (a.act == kActSiluMul) launch_gemv2_r<T, 2, 4>(a, st);
-        else if (a.K >= 8192) launch_gemv2_r<T, 1, 8>(a, st);
-        // small linears (<= 32 M weights): o_proj keeps one row per wave (1024 short-lived workgroups); with the RMSNorm fused — the split-q step's q projection — every
-        // workgroup also normalises the whole input row, so half as many workgroups with two rows per wave win: 8.1 -> 7.5 us (profiles/r05_small_gemv_rp.txt)
-        else if ((size_t)a.N * a.K <= ((size_t)1 << 25)) { if (a.norm_w) launch_gemv2_r<T, 2, 4>(a, st); else launch_gemv2_r<T, 1, 2>(a, st); }
-        else launch_gemv2_r<T, 2, 4>(a, st);
+        switch (gemv2_rp(a)) {
+            case 0: launch_gemv2_r<T, 2, 4>(a, st); break;
+            case 1: launch_gemv2_r<T, 1, 8>(a, st); break;
+            default: launch_gemv2_r<T, 1, 2>(a, st); break;
+        }
         return true;
     }
 }
@@ -839,6 +854,9 @@ void launch_gemv(int dtype, const GemvArgs& a, int MB, hipStream_t st) {
     LMX_REQUIRE(a.ldw >= a.K && ((size_t)a.ldw * es) % 16 == 0 && reinterpret_cast<uintptr_t>(a.W) % 16 == 0, "gemv: weight rows must be 16-byte aligned");
     LMX_REQUIRE(MB == 1 || (a.ldx >= a.K && ((size_t)a.ldx * es) % 16 == 0), "gemv: x rows must be 16-byte aligned");
     LMX_REQUIRE(reinterpret_cast<uintptr_t>(a.X) % 16 == 0 && reinterpret_cast<uintptr_t>(a.norm_w) % 16 == 0, "gemv: x and the norm weights must be 16-byte aligned");
+    // a rotated copy can only be read by the kernel it was laid out for: no other GEMV form may see it
+    if (a.rot) LMX_REQUIRE(a.rot > 0 && MB == 1 && gemv2_applies(dtype, a) && a.ldw == gemv_rot_pitch(a.K),
+                           "gemv: a rotated weight copy needs a single row, the hand-counted 16-bit stream and ldw = gemv_rot_pitch(K)");
     dispatch_dtype(dtype, "gemv", [&](auto t) { launch_gemv_t<LMX_T(t)>(a, MB, st); });
 }
 

@@ -18,7 +18,11 @@ namespace lmx {
 
 constexpr size_t gemv2_smem_bytes(int K, int es) { return (size_t)K * es + 16; }
 
-template <typename T, int R, int P, int GEMV2_NX, bool PUBLISH>
+// ROT: W is the rotated decode copy of the weight (gemv_rot_pitch / launch_gemv_rot_pack, elementwise.hip): rows of whole 1-KiB rounds, zero-filled past K, and
+// physical round p of a row of wave slot s holds logical round (p - krot(s) + NR) mod NR, krot(s) = (s * a.rot) mod NR.  The wave still sums logical round
+// 0, 1, ... (same cc, same fmaf order: the same bits as the plain form on the plain weight), but its loads start krot rounds into the row and wrap, so the waves of
+// a launch stop walking their rows at one common column offset.
+template <typename T, int R, int P, int GEMV2_NX, bool PUBLISH, bool ROT = false>
 __device__ __forceinline__ void gemv2_body(const GemvArgs& a, int bid, char* smem, unsigned long long* gran, unsigned tag, unsigned long long* ts = nullptr) {
     if (ts && threadIdx.x == 0 && (bid & 31) == 0) __hip_atomic_fetch_min(ts + 6, (unsigned long long)__builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // debug timeline (decode_attn.hip)
     static_assert(sizeof(T) == 2, "gemv2: 16-bit weights");
@@ -74,9 +78,18 @@ __device__ __forceinline__ void gemv2_body(const GemvArgs& a, int bid, char* sme
 
     // ---- the first P rounds go out NOW: they do not depend on x --------------------------------------------------------
     ws_u32x4 buf[P][R];
+    int krot = 0;                                             // ROT: the physical round that holds this wave's logical round 0 (wave-uniform)
+    if constexpr (ROT) krot = __builtin_amdgcn_readfirstlane((int)((unsigned)((bid * 4 + wave) * a.rot) % (unsigned)NR));
     auto issue = [&](int p, int j) {                          // round j (wave-uniform) into buffer p; past the row: a dummy load of one hot line
-        const int c = lane + 64 * j;
-        const uint32_t vo = j < NR ? (uint32_t)(c < KC ? c : KC - 1) * 16u : 0u;
+        uint32_t vo;
+        if constexpr (ROT) {                                  // packed rows are whole rounds: every lane of a physical round is inside the row
+            int jp = j + krot;
+            if (jp >= NR) jp -= NR;
+            vo = j < NR ? (uint32_t)(lane + 64 * jp) * 16u : 0u;
+        } else {
+            const int c = lane + 64 * j;
+            vo = j < NR ? (uint32_t)(c < KC ? c : KC - 1) * 16u : 0u;
+        }
 #pragma unroll
         for (int r = 0; r < R; ++r) ws_load(buf[p][r], vo, rsW, j < NR ? roff[r] : 0u);
     };

@@ -65,12 +65,19 @@ struct GemvArgs {
     int N, K;
     int ldx, ldw, ldc, ldr;
     int act;
+    int rot = 0;          // != 0: W is the rotated decode copy made by launch_gemv_rot_pack with this step (ldw = gemv_rot_pitch(K)); MB = 1, hand-counted stream only
 };
 // Preconditions (checked): MB in 1..4, K % 8 == 0, MB rows of x fit LDS; X, W and norm_w 16-byte aligned, weight rows (ldw) and, for MB > 1, x rows (ldx) multiples
 // of 16 bytes (every lane reads 16 bytes at a time); N % 64 == 0 and R == null with kActSiluMul.  C, R and bias need element alignment only.
 void launch_gemv(int dtype, const GemvArgs& a, int MB, hipStream_t st);
 // does launch_gemv(MB = 1) of this shape take the hand-counted weight stream (gemv2.h)?
 bool gemv2_applies(int dtype, const GemvArgs& a);
+// Rotated decode copy of a [N, K] weight for the hand-counted stream (gemv2.h, ROT form): rows of NR = ceil(K / 512) whole 1-KiB rounds (pitch NR * 512 elements,
+// zero-filled past K); row n belongs to wave slot s = n / R (R = gemv2_rows_per_wave of the launch that will read it; with the SiLU.mul row pairing: the slot of
+// the wave that reads row n) and its physical round p holds logical round (p - (s * rot) % NR + NR) % NR.  Same bits out of the GEMV, another walk over memory.
+inline int gemv_rot_pitch(int K) { return ((K / 8 + 63) / 64) * 512; }
+int gemv2_rows_per_wave(const GemvArgs& a);       // rows per wave launch_gemv(MB = 1) gives this shape on the hand-counted stream (N, K, act, norm_w are read)
+void launch_gemv_rot_pack(int dtype, const void* W, int ldw, void* dst, int N, int K, int R, int rot, bool silu, hipStream_t st);
 
 // ---- attention (attention.hip) ------------------------------------------------------------------------------
 // K cache layout  : [n_kv_heads][s_max][D]      (key rows, post-RoPE)

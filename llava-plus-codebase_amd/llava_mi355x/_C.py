@@ -105,6 +105,10 @@ _SIGS = {
     "lmx_model_set_option": (c_int32, [c_void_p, ctypes.c_char_p, c_int32]),
     "lmx_op_gemm": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int32] * 9 + [c_void_p]),
     "lmx_op_gemv": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float] + [c_int32] * 8 + [c_void_p]),
+    "lmx_op_gemv_rot_pitch": (c_int32, [c_int32]),
+    "lmx_op_gemv_rot_rows": (c_int32, [c_int32] * 4),
+    "lmx_op_gemv_rot_pack": (c_int32, [c_int32, c_void_p, c_int32, c_void_p] + [c_int32] * 5 + [c_void_p]),
+    "lmx_op_gemv_rot": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float] + [c_int32] * 4 + [c_void_p]),
     "lmx_op_rmsnorm": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),
     "lmx_op_layernorm": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),
     "lmx_op_rope_kv": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
@@ -120,6 +124,8 @@ _SIGS = {
                                           c_void_p, c_void_p, c_void_p, c_void_p]),
     "lmx_op_decode_kv_attn": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                         c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, c_void_p]),
+    "lmx_op_decode_kv_attn_rot": (c_int32, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                            c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, ctypes.c_uint32, c_void_p, c_void_p, c_void_p]),
     "lmx_op_decode_attn_batch": (c_int32, [c_int32, c_int32, c_void_p, c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                            POINTER(c_void_p), c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int32, c_void_p]),
     "lmx_op_decode_attn_batch_tab_bytes": (c_size_t, [c_int32]),

@@ -61,6 +61,34 @@ def gemv(x, w, bias=None, residual=None, norm_w=None, eps=1e-5, act=_C.ACT_NONE,
     return out
 
 
+def gemv_rot_pack(w, rot, norm=False, act=_C.ACT_NONE, rows_per_wave=None):
+    """Rotated decode copy of a 16-bit weight w [N, K] (contiguous rows, free row stride) for gemv_rot with the same `norm` (an RMSNorm weight will be given) and
+    `act`: [N, pitch] with pitch = whole 1-KiB load rounds, zero past K; physical round p of row n holds logical round (p - (n // R * rot) % NR) % NR.
+    rows_per_wave: R of another reader (decode_kv_attn: 2); default: the single-row launch's own choice for the shape."""
+    _need_cuda_rows(w)
+    N, K = w.shape
+    R = rows_per_wave if rows_per_wave is not None else lib.lmx_op_gemv_rot_rows(N, K, int(bool(norm)), act)
+    out = torch.empty((N, lib.lmx_op_gemv_rot_pitch(K)), dtype=w.dtype, device=w.device)
+    check(lib.lmx_op_gemv_rot_pack(torch_dtype_code(w.dtype), ptr(w), w.stride(0), ptr(out), N, K, R, int(rot), act, stream_handle()), "gemv_rot_pack")
+    return out
+
+
+def gemv_rot(x, w_rot, K, rot, bias=None, residual=None, norm_w=None, eps=1e-5, act=_C.ACT_NONE, out=None):
+    """gemv(x [1, K], w) on the rotated copy w_rot = gemv_rot_pack(w, rot, norm=norm_w is not None, act=act): the same bits, the waves of the launch start
+    their rows at different load rounds.  Shapes the hand-counted 16-bit stream does not take are an error."""
+    _need_cuda(x, w_rot, bias, residual, norm_w)
+    N = w_rot.shape[0]
+    n_out = N // 2 if act == _C.ACT_SILU_MUL else N
+    if out is None:
+        out = torch.empty((1, n_out), dtype=x.dtype, device=x.device)
+    if tuple(x.shape) != (1, K) or w_rot.shape[1] != lib.lmx_op_gemv_rot_pitch(K) or not w_rot.is_contiguous() or tuple(out.shape) != (1, n_out) \
+            or (residual is not None and tuple(residual.shape) != (1, n_out)):
+        raise ValueError("gemv_rot: x [1, K], w_rot [N, pitch(K)] contiguous, residual / out [1, N] (N / 2 for SiLU*mul)")
+    check(lib.lmx_op_gemv_rot(torch_dtype_code(x.dtype), ptr(x), ptr(w_rot), ptr(out), ptr(bias), ptr(residual), ptr(norm_w), eps, N, K, act, int(rot),
+                              stream_handle()), "gemv_rot")
+    return out
+
+
 def rmsnorm(x, w, eps):
     _need_cuda(x, w)
     y = torch.empty_like(x)
@@ -204,15 +232,23 @@ def decode_attn_batch(qkv, kcaches, vtcaches, pos_words, cos_sin, n_heads, n_kv_
     return out
 
 
-def decode_kv_attn(q_row, x, w_kv, norm_w, eps, kcache, vtcache, cos_sin, pos, n_heads, n_kv_heads, head_dim, granules=None, tag=1, timeline=None, scratch=None):
+def decode_kv_attn(q_row, x, w_kv, norm_w, eps, kcache, vtcache, cos_sin, pos, n_heads, n_kv_heads, head_dim, granules=None, tag=1, timeline=None, scratch=None, rot=0):
     """The split-q decode step's second launch: the k | v projection of the (RMS-normalised, when norm_w is given) input row x next to the attention
-    workgroups.  q_row: a [q|k|v]-sized row whose q columns hold the pre-RoPE query (the k | v columns are ignored).  Same effects as gemv + decode_attn_step."""
+    workgroups.  q_row: a [q|k|v]-sized row whose q columns hold the pre-RoPE query (the k | v columns are ignored).  Same effects as gemv + decode_attn_step.
+    rot > 0: w_kv is gemv_rot_pack(k | v rows, rot, rows_per_wave=2), the rotated copy."""
     _need_cuda(q_row, x, w_kv, kcache, vtcache, cos_sin)
     s_max = kcache.shape[1]
     n_split = (s_max + 127) // 128
     ws, cnt, out = scratch if scratch is not None else decode_attn_scratch(n_heads, n_split, head_dim, x.dtype, x.device)
     if granules is None:
         granules = torch.zeros(2 * n_kv_heads * head_dim, dtype=torch.int64, device=x.device)
+    if rot:
+        if w_kv.shape[1] != lib.lmx_op_gemv_rot_pitch(x.shape[-1]) or not w_kv.is_contiguous():
+            raise ValueError("decode_kv_attn: a rotated copy is [2 * n_kv_heads * head_dim, pitch(K)] contiguous")
+        check(lib.lmx_op_decode_kv_attn_rot(torch_dtype_code(x.dtype), head_dim, ptr(q_row), ptr(x), ptr(w_kv), ptr(norm_w), float(eps), x.shape[-1], int(rot),
+                                            ptr(kcache), ptr(vtcache), ptr(cos_sin), int(pos), n_heads, n_kv_heads, s_max, 1.0 / (head_dim ** 0.5), ptr(ws), ptr(cnt),
+                                            ptr(granules), int(tag), ptr(out), ptr(timeline), stream_handle()), "decode_kv_attn_rot")
+        return out
     check(lib.lmx_op_decode_kv_attn(torch_dtype_code(x.dtype), head_dim, ptr(q_row), ptr(x), ptr(w_kv), ptr(norm_w), float(eps), x.shape[-1], w_kv.stride(0),
                                     ptr(kcache), ptr(vtcache), ptr(cos_sin), int(pos), n_heads, n_kv_heads, s_max, 1.0 / (head_dim ** 0.5), ptr(ws), ptr(cnt),
                                     ptr(granules), int(tag), ptr(out), ptr(timeline), stream_handle()), "decode_kv_attn")
