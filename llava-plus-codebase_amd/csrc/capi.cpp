@@ -553,8 +553,7 @@ int lmx_op_gemv(int32_t dtype, const void* x, const void* w, void* c, const void
 // rotated decode copy of a weight (kernels.h: gemv_rot_pitch) and the single-row linear on it: bit-identical to lmx_op_gemv(MB = 1) on the plain weight
 int32_t lmx_op_gemv_rot_pitch(int32_t K) { return K > 0 ? gemv_rot_pitch(K) : 0; }
 int32_t lmx_op_gemv_rot_rows(int32_t N, int32_t K, int32_t has_norm, int32_t act) {
-    GemvArgs g{}; g.N = N; g.K = K; g.act = act; g.norm_w = has_norm ? &g : nullptr;
-    return gemv2_rows_per_wave(g);
+    return gemv2_rows_per_wave(N, K, has_norm != 0, act);
 }
 int lmx_op_gemv_rot_pack(int32_t dtype, const void* w, int32_t ldw, void* w_rot, int32_t N, int32_t K, int32_t rows_per_wave, int32_t rot, int32_t act, void* stream) {
     LMX_API_BEGIN

@@ -354,7 +354,7 @@ void launch_decode_kv_attn(int dtype, int D, const DecAttnArgs& a, const GemvArg
         const int n_attn = a.nh * a.n_split;
         // projection part: 2 rows per wave, 4 rounds in flight — the q|k|v shape's setting; (4, 4) / (4, 2) / (2, 8) / (1, 8) measured 21.1 -> 22.5 / 23.8 / 21.5 / 22.9 us
         // per launch (profiles/r05_kv_attn_rp.txt): the launch is bound by its 86 MB at the streaming rate, not by workgroup count or bytes in flight
-        const dim3 grid((unsigned)(n_attn + cdiv(g.N, 8)));
+        const dim3 grid((unsigned)(n_attn + cdiv(g.N, 4 * kDecodeKvRowsPerWave)));      // four waves per workgroup
         dispatch_head_dim(D, "decode_kv_attn", [&](auto d) {
             constexpr int DD = decltype(d)::value;
             const auto kern = g.rot ? (g.K <= 4096 ? decode_kv_attn_kernel<LMX_T(t), DD, 2, true> : decode_kv_attn_kernel<LMX_T(t), DD, 4, true>)

@@ -160,7 +160,7 @@ void Model::load_weight(const std::string& name, const void* src, int dtype, int
     const int nh = cfg.n_heads, nkv = cfg.n_kv_heads, I = cfg.intermediate_size;
 
     if (name == "model.embed_tokens.weight") { expect({V, H}); plain(embed); }
-    else if (name == "model.norm.weight") { expect({H}); plain(final_norm); }
+    else if (name == "model.norm.weight") { expect({H}); plain(final_norm); pack_rot_head(st); }      // (the head's launch fuses it: see input_layernorm below)
     else if (name == "lm_head.weight") {
         expect({V, H});
         if (V_l == V) plain(lm_head);
@@ -179,10 +179,11 @@ void Model::load_weight(const std::string& name, const void* src, int dtype, int
         const std::string sub = name.substr(dot + 1);
         DecLayerW& w = dec[li];
         if (!w.wqkv) {
-            w.wqkv = alloc_weight((size_t)qkv_n * H * es);
-            w.wo = alloc_weight((size_t)H * nh_l * D * es);
-            w.wgu = alloc_weight((size_t)2 * I_l * H * es, I_l != I_sh);
-            w.wd = alloc_weight((size_t)H * I_l * es, I_l != I_sh);
+            auto bytes = [&](DecSite site) { const DecLinear d = dec_linear(site, &w); return (size_t)d.N * d.K * es; };
+            w.wqkv = alloc_weight(bytes(DecSite::QKV));
+            w.wo = alloc_weight(bytes(DecSite::O));
+            w.wgu = alloc_weight(bytes(DecSite::GateUp), I_l != I_sh);
+            w.wd = alloc_weight(bytes(DecSite::Down), I_l != I_sh);
         }
         if (sub == "self_attn.q_proj.weight") { expect({(int64_t)nh * D, H}); copy_block(w.wqkv, H, 0, src, H, r * nh_l * D, 0, nh_l * D, H, es, st); pack_rot_layer(w, kRotQ, st); }
         else if (sub == "self_attn.k_proj.weight") { expect({(int64_t)nkv * D, H}); copy_block(w.wqkv, H, nh_l * D, src, H, r * nkv_l * D, 0, nkv_l * D, H, es, st); pack_rot_layer(w, kRotKv, st); }
@@ -191,7 +192,8 @@ void Model::load_weight(const std::string& name, const void* src, int dtype, int
         else if (sub == "mlp.gate_proj.weight") { expect({I, H}); launch_interleave_half(cfg.dtype, static_cast<const char*>(src) + (size_t)r * I_sh * H * es, w.wgu, I_sh, H, 0, st); }
         else if (sub == "mlp.up_proj.weight") { expect({I, H}); launch_interleave_half(cfg.dtype, static_cast<const char*>(src) + (size_t)r * I_sh * H * es, w.wgu, I_sh, H, 1, st); }
         else if (sub == "mlp.down_proj.weight") { expect({H, I}); copy_block(w.wd, I_l, 0, src, I, 0, r * I_sh, H, I_sh, es, st); pack_rot_layer(w, kRotDown, st); }
-        else if (sub == "input_layernorm.weight") { expect({H}); plain(w.ln1); }
+        // the q launch fuses this norm, and whether a launch fuses one is part of what decides its rows per wave: a q copy packed before the norm arrived follows now
+        else if (sub == "input_layernorm.weight") { expect({H}); plain(w.ln1); pack_rot_layer(w, kRotQ, st); }
         else if (sub == "post_attention_layernorm.weight") { expect({H}); plain(w.ln2); }
         else if (sub == "self_attn.rotary_emb.inv_freq") { return; }   // buffer in old checkpoints; recomputed
         else throw Error{"unknown decoder tensor: " + name};
@@ -297,27 +299,58 @@ void Model::finalize() {
     if (opt_rot) ensure_rot_weights(nullptr);
 }
 
-// ---- rotated decode copies (engine.h) ---------------------------------------------------------------------------------
-// Each copy is laid out for the rows-per-wave of the launch that reads it, so the shapes here are decode_step_launch's (N, K, norm, activation).
-void Model::pack_rot(void*& dst, const void* W, const GemvArgs& launch, int R, hipStream_t st) {
-    if (!dst) dst = alloc_weight((size_t)launch.N * gemv_rot_pitch(launch.K) * es);
-    launch_gemv_rot_pack(cfg.dtype, W, launch.K, dst, launch.N, launch.K, R, kRotStep, false, st);
+// ---- the decoder's linears (engine.h: DecLinear) ------------------------------------------------------------------------
+DecLinear Model::dec_linear(DecSite site, const DecLayerW* w) const {
+    const int q_n = nh_l * D, kv_n = 2 * nkv_l * D;
+    DecLinear d;
+    switch (site) {
+        case DecSite::QKV: d.W = w->wqkv; d.Wsw = w->sw_qkv; d.N = d.ldc = qkv_n; d.K = H; d.norm = w->ln1; break;
+        case DecSite::Q: d.W = w->wqkv; d.Wrot = w->rot_q; d.N = d.ldc = q_n; d.K = H; d.norm = w->ln1; break;
+        case DecSite::KV:      // rows [q_n, q_n + kv_n) of the fused q|k|v weight
+            d.W = w->wqkv ? static_cast<const char*>(w->wqkv) + (size_t)q_n * H * es : nullptr; d.Wrot = w->rot_kv; d.N = d.ldc = kv_n; d.K = H; d.norm = w->ln1; break;
+        case DecSite::O: d.W = w->wo; d.Wsw = w->sw_o; d.Wrot = w->rot_o; d.N = d.ldc = H; d.K = q_n; d.residual = true; break;
+        case DecSite::GateUp: d.W = w->wgu; d.Wsw = w->sw_gu; d.N = 2 * I_l; d.ldc = I_l; d.K = H; d.act = kActSiluMul; d.norm = w->ln2; break;
+        case DecSite::Down: d.W = w->wd; d.Wsw = w->sw_d; d.Wrot = w->rot_d; d.N = d.ldc = H; d.K = I_l; d.residual = true; break;
+        // vocabulary-parallel head: this rank's V_l rows fill columns [v_off, v_off + V_l) of a [V] row
+        case DecSite::Head: d.W = lm_head; d.Wsw = sw_lm_head; d.Wrot = rot_lm_head; d.N = V_l; d.ldc = V; d.c_off = v_off; d.K = H; d.norm = final_norm; break;
+    }
+    return d;
 }
-static GemvArgs rot_shape(int N, int K, const void* norm_w) { GemvArgs g{}; g.N = N; g.K = K; g.norm_w = norm_w; return g; }
+
+GemvArgs Model::gemv_args(const DecLinear& d, const void* x, void* out) const {
+    void* c = out ? static_cast<char*>(out) + (size_t)d.c_off * es : nullptr;
+    GemvArgs g{x, d.W, c, nullptr, d.residual && cfg.tp_rank == 0 ? c : nullptr, d.norm, d.norm ? cfg.rms_eps : 0.f, d.N, d.K, d.K, d.K, d.ldc, d.residual ? d.ldc : 0, d.act};
+    if (opt_rot && d.Wrot) { g.W = d.Wrot; g.ldw = gemv_rot_pitch(d.K); g.rot = kRotStep; }
+    return g;
+}
+
+GemmArgs Model::gemm_args(const DecLinear& d, const void* x, void* out, int M) const {
+    void* c = static_cast<char*>(out) + (size_t)d.c_off * es;
+    return GemmArgs{x, d.W, c, nullptr, d.residual && cfg.tp_rank == 0 ? c : nullptr, M, d.N, d.K, d.K, d.K, d.ldc, d.residual ? d.ldc : 0, d.act};
+}
+
+// ---- rotated decode copies (engine.h) ---------------------------------------------------------------------------------
+// Each copy is laid out for the rows-per-wave of the launch that reads it: the k|v rows go through the split-q launch (kernels.h), every other site through
+// launch_gemv, whose rule reads the very GemvArgs decode_step_launch builds for the site.
+int Model::rot_rows(DecSite site, const DecLinear& d) const {
+    return site == DecSite::KV ? kDecodeKvRowsPerWave : gemv2_rows_per_wave(gemv_args(d, nullptr, nullptr));
+}
+void Model::pack_rot(void*& dst, DecSite site, const DecLayerW* w, hipStream_t st) {
+    const DecLinear d = dec_linear(site, w);
+    if (!d.W) return;
+    if (!dst) dst = alloc_weight((size_t)d.N * gemv_rot_pitch(d.K) * es);
+    launch_gemv_rot_pack(cfg.dtype, d.W, d.K, dst, d.N, d.K, rot_rows(site, d), kRotStep, false, st);
+}
 
 void Model::pack_rot_layer(DecLayerW& w, int which, hipStream_t st) {
     which &= rot_live;
-    const int q_n = nh_l * D, kv_n = 2 * nkv_l * D;
-    if ((which & kRotDown) && w.wd) { const GemvArgs g = rot_shape(H, I_l, nullptr); pack_rot(w.rot_d, w.wd, g, gemv2_rows_per_wave(g), st); }
-    if ((which & kRotO) && w.wo) { const GemvArgs g = rot_shape(H, q_n, nullptr); pack_rot(w.rot_o, w.wo, g, gemv2_rows_per_wave(g), st); }
-    if ((which & kRotQ) && w.wqkv) { const GemvArgs g = rot_shape(q_n, H, w.wqkv);      /* non-null norm_w: the launch fuses the RMSNorm, which decides its rows per wave */ pack_rot(w.rot_q, w.wqkv, g, gemv2_rows_per_wave(g), st); }
-    // decode_kv_attn_kernel's projection part: 2 rows per wave
-    if ((which & kRotKv) && w.wqkv) pack_rot(w.rot_kv, static_cast<const char*>(w.wqkv) + (size_t)q_n * H * es, rot_shape(kv_n, H, nullptr), 2, st);
+    if (which & kRotDown) pack_rot(w.rot_d, DecSite::Down, &w, st);
+    if (which & kRotO) pack_rot(w.rot_o, DecSite::O, &w, st);
+    if (which & kRotQ) pack_rot(w.rot_q, DecSite::Q, &w, st);
+    if (which & kRotKv) pack_rot(w.rot_kv, DecSite::KV, &w, st);
 }
 void Model::pack_rot_head(hipStream_t st) {
-    if (!(rot_live & kRotHead) || !lm_head) return;
-    const GemvArgs g = rot_shape(V_l, H, lm_head);      // (non-null norm_w: the launch fuses the final norm)
-    pack_rot(rot_lm_head, lm_head, g, gemv2_rows_per_wave(g), st);
+    if (rot_live & kRotHead) pack_rot(rot_lm_head, DecSite::Head, nullptr, st);
 }
 
 void Model::ensure_rot_weights(hipStream_t st) {
@@ -325,11 +358,12 @@ void Model::ensure_rot_weights(hipStream_t st) {
     if (cfg.dtype == kF32) return;
     LMX_CHECK_HIP(hipDeviceSynchronize());                   // the sources may have been written on any stream
     // a copy only where the launch that would read it exists: the hand-counted stream over the packed pitch (32-bit row offsets); q and k|v: the split-q step
-    auto fits = [&](int N, int K) { GemvArgs g = rot_shape(N, K, nullptr); g.ldw = gemv_rot_pitch(K); return gemv2_applies(cfg.dtype, g); };
-    const int q_n = nh_l * D, kv_n = 2 * nkv_l * D;
-    GemvArgs gkv = rot_shape(kv_n, H, nullptr); gkv.ldw = gemv_rot_pitch(H);
-    const bool splitq_ok = decode_kv_attn_applies(cfg.dtype, D, gkv) && s_max % 128 == 0 && s_max / 128 <= 32;
-    const int live = (fits(H, I_l) ? kRotDown : 0) | (fits(H, q_n) ? kRotO : 0) | (fits(V_l, H) ? kRotHead : 0) | (splitq_ok ? kRotKv : 0) | (splitq_ok && fits(q_n, H) ? kRotQ : 0);
+    const DecLayerW any;                                     // a site's shape is every layer's
+    auto on_copy = [&](DecSite site) { GemvArgs g = gemv_args(dec_linear(site, &any), nullptr, nullptr); g.ldw = gemv_rot_pitch(g.K); return g; };
+    auto fits = [&](DecSite site) { return gemv2_applies(cfg.dtype, on_copy(site)); };
+    const bool splitq_ok = decode_kv_attn_applies(cfg.dtype, D, on_copy(DecSite::KV)) && s_max % 128 == 0 && s_max / 128 <= 32;
+    const int live = (fits(DecSite::Down) ? kRotDown : 0) | (fits(DecSite::O) ? kRotO : 0) | (fits(DecSite::Head) ? kRotHead : 0) | (splitq_ok ? kRotKv : 0) |
+                     (splitq_ok && fits(DecSite::Q) ? kRotQ : 0);
     const int fresh = rot_set & live & ~rot_live;            // nothing to do on a second call
     rot_live |= fresh;
     if (!fresh) return;
@@ -666,7 +700,6 @@ void Model::prefill_piece(const PrefillWs& ws, const std::vector<PrefillSeg>& se
     const int dt = cfg.dtype;
     const float scale = 1.f / sqrtf((float)D);
     const int gv = cfg.gemm_variant;
-    const bool lead = cfg.tp_rank == 0;
     auto with_scratch = [&](GemmArgs g) { g.skw = ws.skw; return g; };
     auto at = [&](void* base, int r0, size_t width) { return static_cast<char*>(base) + (size_t)r0 * width * es; };
     for (const PrefillSeg& g : seg) LMX_CHECK_HIP(hipMemcpyAsync(at(ws.h, g.row0, H), g.src, (size_t)g.n * H * es, hipMemcpyDeviceToDevice, st));
@@ -683,7 +716,7 @@ void Model::prefill_piece(const PrefillWs& ws, const std::vector<PrefillSeg>& se
         const bool qf = o.fuse_rope && seg.size() == 1 && gv == 0 && opt_fuse_rope && gemm_fuses_qkv(dt, n, H, D, nh_l, nkv_l, qpos, s_max, false);
         {
             LMX_PROF_K("prefill.gemm.qkv");
-            GemmArgs g = with_scratch(GemmArgs{xr, w.wqkv, qr, nullptr, nullptr, n, qkv_n, H, H, H, qkv_n, 0, kActNone});
+            GemmArgs g = with_scratch(gemm_args(dec_linear(DecSite::QKV, &w), xr, qr, n));
             if (qf) { g.qf_rope = rope; g.qf_kc = kc(g0.s); g.qf_vt = vt(g0.s); g.qf_pos0 = qpos; g.qf_nh = nh_l; g.qf_nkv = nkv_l; g.qf_smax = s_max; g.qf_D = D; }
             launch_gemm(dt, g, gv, st);
         }
@@ -700,14 +733,14 @@ void Model::prefill_piece(const PrefillWs& ws, const std::vector<PrefillSeg>& se
             if (dt == kF32) launch_decode_attn(dt, D, DecodeAttnArgs{qa, aa, kca, vta, nullptr, pos, m, 0, 1, qkv_n, nh_l * D, nh_l, nkv_l, s_max, 1, scale, ws.aws}, st);
             else launch_flash_prefill(dt, D, FlashArgs{qa, aa, kca, vta, m, pos + m, pos, qkv_n, nh_l * D, nh_l, nkv_l, s_max, scale, 1}, st);
         }
-        { LMX_PROF_K("prefill.gemm.o"); launch_gemm(dt, with_scratch(GemmArgs{ar, w.wo, hr, nullptr, lead ? hr : nullptr, n, H, nh_l * D, nh_l * D, nh_l * D, H, H, kActNone}), gv, st); }
+        { LMX_PROF_K("prefill.gemm.o"); launch_gemm(dt, with_scratch(gemm_args(dec_linear(DecSite::O, &w), ar, hr, n)), gv, st); }
     };
     auto mlp_block = [&](int l, int r0, int n) {
         const DecLayerW& w = dec[l];
         void *hr = at(ws.h, r0, H), *xr = at(ws.x, r0, H), *cr = at(ws.act, r0, I_l);
         { LMX_PROF("prefill.rmsnorm"); launch_rmsnorm(dt, hr, w.ln2, xr, n, H, H, H, cfg.rms_eps, st); }
-        { LMX_PROF_K("prefill.gemm.gate_up"); launch_gemm(dt, with_scratch(GemmArgs{xr, w.wgu, cr, nullptr, nullptr, n, 2 * I_l, H, H, H, I_l, 0, kActSiluMul}), gv, st); }
-        { LMX_PROF_K("prefill.gemm.down"); launch_gemm(dt, with_scratch(GemmArgs{cr, w.wd, hr, nullptr, lead ? hr : nullptr, n, H, I_l, I_l, I_l, H, H, kActNone}), gv, st); }
+        { LMX_PROF_K("prefill.gemm.gate_up"); launch_gemm(dt, with_scratch(gemm_args(dec_linear(DecSite::GateUp, &w), xr, cr, n)), gv, st); }
+        { LMX_PROF_K("prefill.gemm.down"); launch_gemm(dt, with_scratch(gemm_args(dec_linear(DecSite::Down, &w), cr, hr, n)), gv, st); }
     };
     // The two-half pipeline hides 35-55 % of the all-reduce time but costs GEMM efficiency (each half alone cannot fill the chip): measured with a
     // timed stand-in all-reduce (tools/mb_tp_overlap.py, 7B shards) it wins from rows x ranks >= 4096 on — TP=2 at 2048 rows, TP=8 at 1087 —
@@ -762,7 +795,7 @@ void Model::prefill_head(Seq* s, const void* h_row, void* dst, bool pick, hipStr
     const int dt = cfg.dtype;
     // vocabulary-parallel head: this rank computes columns [v_off, v_off + V_l) of a zeroed row, the sum over ranks completes it
     if (V_l != V) LMX_CHECK_HIP(hipMemsetAsync(dst, 0, (size_t)V * es, st));
-    { LMX_PROF_K("prefill.gemv.lm_head"); launch_gemv(dt, rot_args(GemvArgs{h_row, lm_head, static_cast<char*>(dst) + (size_t)v_off * es, nullptr, nullptr, final_norm, cfg.rms_eps, V_l, H, H, H, V, 0, kActNone}, rot_lm_head, kRotStep), 1, st); }
+    { LMX_PROF_K("prefill.gemv.lm_head"); launch_gemv(dt, gemv_args(dec_linear(DecSite::Head), h_row, dst), 1, st); }
     gather_logits(dst, 1, st);
     if (!pick) return;
     // with logits processors: the ruled pick (history = the prompt ids + whatever the log holds: nothing, for a request's first token)
@@ -805,7 +838,7 @@ void Model::prefill(Seq* s, const void* embeds, int T, int chunk, void* logits, 
             char* lc = static_cast<char*>(logits) + (size_t)c0 * V * es;
             launch_rmsnorm(dt, ws.h, final_norm, ws.x, tc, H, H, H, cfg.rms_eps, st);
             if (V_l != V) LMX_CHECK_HIP(hipMemsetAsync(lc, 0, (size_t)tc * V * es, st));
-            launch_gemm(dt, GemmArgs{ws.x, lm_head, lc + (size_t)v_off * es, nullptr, nullptr, tc, V_l, H, H, H, V, 0, kActNone}, cfg.gemm_variant, st);
+            launch_gemm(dt, gemm_args(dec_linear(DecSite::Head), ws.x, lc, tc), cfg.gemm_variant, st);
             gather_logits(lc, tc, st);
         }
         if (c0 + tc == T && (greedy || (logits && !logits_all)))
@@ -878,12 +911,10 @@ void Seq::check_wait_status(hipStream_t st) {
 // projection, so that the attention's latency chain runs under the k|v weight stream — bit-identical to the three-launch form.
 void Model::decode_step_launch(Seq* s, hipStream_t st, int64_t* id_out) {
     const int dt = cfg.dtype;
-    const bool lead = cfg.tp_rank == 0;
     const float scale = 1.f / sqrtf((float)D);
     // s->d_h holds the embedding of the token to feed: put there by decode() / decode_batch() before the first step and by the
     // fused pick kernel at the end of every step
     const bool attn16 = (dt == kBF16 || dt == kF16) && s_max % 128 == 0 && s_max / 128 <= 32;      // the chunked launch with the position by value
-    const int q_n = nh_l * D, kv_n = 2 * nkv_l * D;
     for (int l = 0; l < L; ++l) {
         const DecLayerW& w = dec[l];
         void* kc = s->kc.as<char>() + (size_t)l * s->layer_stride;
@@ -893,16 +924,15 @@ void Model::decode_step_launch(Seq* s, hipStream_t st, int64_t* id_out) {
         // only the 128-key chunks that exist are launched: the host mirrors the position (s->len == *d_len while this step is queued)
         a.pos = s->len; a.n_split = s->len / 128 + 1; a.nh = nh_l; a.nkv = nkv_l; a.s_max = s_max; a.scale = scale;
         a.status = s->d_status;                      // both forms: the merger's wait for the other chunks is bounded in either
-        // rows [q_n, q_n + kv_n) of the fused q|k|v weight: the k | v projection of the split-q form
-        const GemvArgs gkv{s->d_h, static_cast<const char*>(w.wqkv) + (size_t)q_n * H * es, nullptr, nullptr, nullptr, w.ln1, cfg.rms_eps, kv_n, H, H, H, kv_n, 0, kActNone};
+        const GemvArgs gkv = gemv_args(dec_linear(DecSite::KV, &w), s->d_h, nullptr);      // the k | v projection of the split-q form: its rows leave as granules
         if (attn16 && splitq_allowed() && decode_kv_attn_applies(dt, D, gkv)) {
-            { LMX_PROF_K("decode.gemv.q"); launch_gemv(dt, rot_args(GemvArgs{s->d_h, w.wqkv, s->d_qkv, nullptr, nullptr, w.ln1, cfg.rms_eps, q_n, H, H, H, q_n, 0, kActNone}, w.rot_q, kRotStep), 1, st); }
+            { LMX_PROF_K("decode.gemv.q"); launch_gemv(dt, gemv_args(dec_linear(DecSite::Q, &w), s->d_h, s->d_qkv), 1, st); }
             a.kv_gran = s->kv_gran.as<unsigned long long>(); a.tag = s->attn_tag;
             if (debug_splitq_timeout.load(std::memory_order_relaxed) > 0 && debug_splitq_timeout.fetch_sub(1) > 0) a.pub_tag = a.tag ^ 0x40000000u;
             s->attn_tag = s->attn_tag >= 0xfffffff0u ? 1u : s->attn_tag + 1;
-            { LMX_PROF_K("decode.kv_attn"); launch_decode_kv_attn(dt, D, a, rot_args(gkv, w.rot_kv, kRotStep), st); }
+            { LMX_PROF_K("decode.kv_attn"); launch_decode_kv_attn(dt, D, a, gkv, st); }
         } else {
-            { LMX_PROF_K("decode.gemv.qkv"); launch_gemv(dt, GemvArgs{s->d_h, w.wqkv, s->d_qkv, nullptr, nullptr, w.ln1, cfg.rms_eps, qkv_n, H, H, H, qkv_n, 0, kActNone}, 1, st); }
+            { LMX_PROF_K("decode.gemv.qkv"); launch_gemv(dt, gemv_args(dec_linear(DecSite::QKV, &w), s->d_h, s->d_qkv), 1, st); }
             LMX_PROF("decode.attn");
             if (attn16) launch_decode_attn_step(dt, D, a, st);
             else {
@@ -910,14 +940,14 @@ void Model::decode_step_launch(Seq* s, hipStream_t st, int64_t* id_out) {
                 launch_decode_fused(dt, D, fa, st);
             }
         }
-        { LMX_PROF_K("decode.gemv.o"); launch_gemv(dt, rot_args(GemvArgs{s->d_attn, w.wo, s->d_h, nullptr, lead ? s->d_h : nullptr, nullptr, 0.f, H, nh_l * D, nh_l * D, nh_l * D, H, H, kActNone}, w.rot_o, kRotStep), 1, st); }
+        { LMX_PROF_K("decode.gemv.o"); launch_gemv(dt, gemv_args(dec_linear(DecSite::O, &w), s->d_attn, s->d_h), 1, st); }
         { LMX_PROF_AR("decode.allreduce"); allreduce(s->d_h, (size_t)H, st); }
-        { LMX_PROF_K("decode.gemv.gate_up"); launch_gemv(dt, GemvArgs{s->d_h, w.wgu, s->d_act, nullptr, nullptr, w.ln2, cfg.rms_eps, 2 * I_l, H, H, H, I_l, 0, kActSiluMul}, 1, st); }
-        { LMX_PROF_K("decode.gemv.down"); launch_gemv(dt, rot_args(GemvArgs{s->d_act, w.wd, s->d_h, nullptr, lead ? s->d_h : nullptr, nullptr, 0.f, H, I_l, I_l, I_l, H, H, kActNone}, w.rot_d, kRotStep), 1, st); }
+        { LMX_PROF_K("decode.gemv.gate_up"); launch_gemv(dt, gemv_args(dec_linear(DecSite::GateUp, &w), s->d_h, s->d_act), 1, st); }
+        { LMX_PROF_K("decode.gemv.down"); launch_gemv(dt, gemv_args(dec_linear(DecSite::Down, &w), s->d_act, s->d_h), 1, st); }
         allreduce(s->d_h, (size_t)H, st);
     }
     if (V_l != V) LMX_CHECK_HIP(hipMemsetAsync(s->d_logits, 0, (size_t)V * es, st));
-    { LMX_PROF_K("decode.gemv.lm_head"); launch_gemv(dt, rot_args(GemvArgs{s->d_h, lm_head, static_cast<char*>(s->d_logits) + (size_t)v_off * es, nullptr, nullptr, final_norm, cfg.rms_eps, V_l, H, H, H, V, 0, kActNone}, rot_lm_head, kRotStep), 1, st); }
+    { LMX_PROF_K("decode.gemv.lm_head"); launch_gemv(dt, gemv_args(dec_linear(DecSite::Head), s->d_h, s->d_logits), 1, st); }
     { ProfScope ps_ag(this, V_l != V ? "decode.allgather.logits" : nullptr, st); gather_logits(s->d_logits, 1, st); }
     {
         LMX_PROF("decode.argmax");      // pick (argmax | draw) + *len += 1 + token log + next token's embedding row -> d_h, one launch
@@ -971,19 +1001,19 @@ void Model::ensure_batch_weights(hipStream_t st) {
     batch_weights_ready = true;
     const char* e = getenv("LMX_BATCH_SWIZZLE");
     if (cfg.dtype == kF32 || (e && atoi(e) == 0)) return;
-    auto mk = [&](const void* W, int N, int K) -> void* {
-        if (!W) return nullptr;
-        void* d = alloc_weight(skinny_swizzled_bytes(N, K, es));
-        launch_skinny_swizzle(cfg.dtype, W, K, d, N, K, st);
-        return d;
+    auto mk = [&](const DecLinear& d) -> void* {
+        if (!d.W) return nullptr;
+        void* sw = alloc_weight(skinny_swizzled_bytes(d.N, d.K, es));
+        launch_skinny_swizzle(cfg.dtype, d.W, d.K, sw, d.N, d.K, st);
+        return sw;
     };
     for (auto& w : dec) {
-        w.sw_qkv = mk(w.wqkv, qkv_n, H);
-        w.sw_o = mk(w.wo, H, nh_l * D);
-        w.sw_gu = mk(w.wgu, 2 * I_l, H);
-        w.sw_d = mk(w.wd, H, I_l);
+        w.sw_qkv = mk(dec_linear(DecSite::QKV, &w));
+        w.sw_o = mk(dec_linear(DecSite::O, &w));
+        w.sw_gu = mk(dec_linear(DecSite::GateUp, &w));
+        w.sw_d = mk(dec_linear(DecSite::Down, &w));
     }
-    sw_lm_head = mk(lm_head, V_l, H);
+    sw_lm_head = mk(dec_linear(DecSite::Head));
     LMX_CHECK_HIP(hipStreamSynchronize(st));
 }
 
@@ -1061,19 +1091,20 @@ void Model::decode_batch(Batch* b, Seq* const* seqs, int n, const int64_t* token
             if (tokens[i] >= 0) launch_set_state(seqs[i]->d_len, -1, seqs[i]->d_tok, tokens[i], 1, seqs[i]->d_nout, -1, st);
 
     const int dt = cfg.dtype;
-    const bool lead = cfg.tp_rank == 0;
     const float scale = 1.f / sqrtf((float)D);
     // A batch row-block linear y = act(norm(x) W^T) (+ residual): rmsnorm launch + the skinny MFMA kernel on the fragment-order weight
     // copy for up to 32 rows (7B, per step: 2 rows ~3.3 ms, 8 rows 4.2 ms, 32 rows 8.8 ms; the multi-row GEMV chain measured 3.75 ms at
     // 2 rows and 5.05 ms at 4, so it is not used); fp32 verification engine / larger batches: prefill GEMM family.
-    auto linear = [&](const void* x_in, const void* norm_w, void* x_normed, GemmArgs g, const void* wsw) {
-        if (norm_w) {
+    // x_ready: b->x already holds the normalised rows (allreduce_norm's hand-over); otherwise a linear with a norm in front takes b->h through it into b->x
+    auto linear = [&](const DecLinear& d, const void* x, bool x_ready, void* out) {
+        if (d.norm && !x_ready) {
             LMX_PROF("decode_batch.rmsnorm");
-            launch_rmsnorm(dt, x_in, norm_w, x_normed, g.M, g.K, g.ldx, g.K, cfg.rms_eps, st);
-            g.X = x_normed; g.ldx = g.K;
+            launch_rmsnorm(dt, x, d.norm, b->x, n, d.K, d.K, d.K, cfg.rms_eps, st);
+            x = b->x;
         }
         LMX_PROF("decode_batch.linear");
-        if (dt != kF32 && g.M <= 32) { g.Wsw = wsw; g.skw = b->sk_scratch.p; g.sk_cnt = b->sk_cnt.as<int>(); launch_skinny_gemm(dt, g, st); } else launch_gemm(dt, g, cfg.gemm_variant, st);
+        GemmArgs g = gemm_args(d, x, out, n);
+        if (dt != kF32 && g.M <= 32) { g.Wsw = d.Wsw; g.skw = b->sk_scratch.p; g.sk_cnt = b->sk_cnt.as<int>(); launch_skinny_gemm(dt, g, st); } else launch_gemm(dt, g, cfg.gemm_variant, st);
     };
     if (n == 1) {
         // a lone member takes the single-sequence step (GEMV with fused RMSNorm: fewer launches, full-rate weight stream)
@@ -1090,7 +1121,7 @@ void Model::decode_batch(Batch* b, Seq* const* seqs, int n, const int64_t* token
         bool x_ready = false;          // b->x already holds the normalised rows of the NEXT linear (written by the tensor-parallel all-reduce's launch: allreduce_norm)
         for (int l = 0; l < L; ++l) {
             const DecLayerW& w = dec[l];
-            linear(x_ready ? b->x : b->h, x_ready ? nullptr : w.ln1, b->x, GemmArgs{x_ready ? b->x : b->h, w.wqkv, b->qkv, nullptr, nullptr, n, qkv_n, H, H, H, qkv_n, 0, kActNone}, w.sw_qkv);
+            linear(dec_linear(DecSite::QKV, &w), x_ready ? b->x : b->h, x_ready, b->qkv);
             {
                 LMX_PROF("decode_batch.attn");
                 int max_len = 0;
@@ -1100,14 +1131,14 @@ void Model::decode_batch(Batch* b, Seq* const* seqs, int n, const int64_t* token
                 a.tab = b->d_attn_tab + (size_t)l * b->cap; a.n_seq = n; a.qkv_stride = qkv_n; a.o_stride = nh_l * D;
                 launch_decode_fused(dt, D, a, st);
             }
-            linear(b->attn, nullptr, nullptr, GemmArgs{b->attn, w.wo, b->h, nullptr, lead ? b->h : nullptr, n, H, nh_l * D, nh_l * D, nh_l * D, H, H, kActNone}, w.sw_o);
+            linear(dec_linear(DecSite::O, &w), b->attn, false, b->h);
             { LMX_PROF_AR("decode_batch.allreduce"); x_ready = allreduce_norm(b->h, n, w.ln2, b->x, st); }
-            linear(x_ready ? b->x : b->h, x_ready ? nullptr : w.ln2, b->x, GemmArgs{x_ready ? b->x : b->h, w.wgu, b->act, nullptr, nullptr, n, 2 * I_l, H, H, H, I_l, 0, kActSiluMul}, w.sw_gu);
-            linear(b->act, nullptr, nullptr, GemmArgs{b->act, w.wd, b->h, nullptr, lead ? b->h : nullptr, n, H, I_l, I_l, I_l, H, H, kActNone}, w.sw_d);
+            linear(dec_linear(DecSite::GateUp, &w), x_ready ? b->x : b->h, x_ready, b->act);
+            linear(dec_linear(DecSite::Down, &w), b->act, false, b->h);
             x_ready = allreduce_norm(b->h, n, l + 1 < L ? dec[l + 1].ln1 : final_norm, b->x, st);       // the next layer's input norm (or the final one) rides in the same launch
         }
         if (V_l != V) LMX_CHECK_HIP(hipMemsetAsync(b->logits, 0, (size_t)n * V * es, st));
-        linear(x_ready ? b->x : b->h, x_ready ? nullptr : final_norm, b->x, GemmArgs{x_ready ? b->x : b->h, lm_head, static_cast<char*>(b->logits) + (size_t)v_off * es, nullptr, nullptr, n, V_l, H, H, H, V, 0, kActNone}, sw_lm_head);
+        linear(dec_linear(DecSite::Head), x_ready ? b->x : b->h, x_ready, b->logits);
         gather_logits(b->logits, n, st);
         // pick + advance + the picked tokens' embedding rows -> b->h (input of the next step), one launch
         { LMX_PROF("decode_batch.argmax"); launch_argmax_advance_batch(dt, b->logits, Vr, V, b->d_state_tab, nullptr, n, d_ids + (size_t)step * b->cap, embed, b->h, H, st, any_rules); }

@@ -50,6 +50,18 @@ struct DecLayerW {
     void *sw_qkv = nullptr, *sw_o = nullptr, *sw_gu = nullptr, *sw_d = nullptr;   // fragment-order copies for the decode-batch kernel
     void *rot_d = nullptr, *rot_kv = nullptr, *rot_q = nullptr, *rot_o = nullptr;   // rotated decode copies: wd, the k|v rows and the q rows of wqkv, wo (Model::ensure_rot_weights)
 };
+// The decoder's linears, as the layer walks launch them: q|k|v whole (prefill, decode batch, three-launch decode step), its q rows and its k|v rows (split-q
+// decode step), o_proj, gate|up, down_proj, lm_head
+enum class DecSite { QKV, Q, KV, O, GateUp, Down, Head };
+// y = act(RMSNorm(x) W^T) (+ residual) of one site (Model::dec_linear)
+struct DecLinear {
+    const void *W = nullptr, *Wsw = nullptr, *Wrot = nullptr;      // plain [N][K] | fragment-order copy (decode batch) | rotated decode copy; null where absent
+    int N = 0, K = 0;
+    int ldc = 0, c_off = 0;            // output pitch (N; I_l under SiLU·mul; V for the head) and first output column (the head's v_off)
+    int act = kActNone;
+    const void* norm = nullptr;        // weight of the RMSNorm in front of it (ln1, ln2, final_norm), or null
+    bool residual = false;             // adds the residual stream (on the lead rank)
+};
 struct VisLayerW {
     void *wqkv = nullptr, *bqkv = nullptr, *wo = nullptr, *bo = nullptr, *fc1 = nullptr, *b1 = nullptr, *fc2 = nullptr, *b2 = nullptr;
     void *ln1w = nullptr, *ln1b = nullptr, *ln2w = nullptr, *ln2b = nullptr;
@@ -71,25 +83,30 @@ struct Model {
     std::vector<DevBuf> pool;   // owns every weight allocation
     void* embed = nullptr; void* final_norm = nullptr; void* lm_head = nullptr; void* sw_lm_head = nullptr;
     bool batch_weights_ready = false;
+    // One description per decoder linear, built on demand (nothing is stored, and it works while load_weight is still filling the tensors in).  Every launch of the
+    // three layer walks and every weight copy derives from it.  `w`: the layer; the head needs none.
+    DecLinear dec_linear(DecSite site, const DecLayerW* w = nullptr) const;
+    // GEMV form (decode step, prefill_head): the norm fused, the residual = out on the lead rank, the rotated copy when the option is on and the copy exists
+    GemvArgs gemv_args(const DecLinear& d, const void* x, void* out) const;
+    // GEMM form (prefill_piece, the logits_all head, the decode batch): M rows the caller has already normalised; qf_*, skw and Wsw stay with the callers
+    GemmArgs gemm_args(const DecLinear& d, const void* x, void* out, int M) const;
     // Rotated decode copies (kernels.h: gemv_rot_pitch) of the weights whose batch-1 decode launch gains from waves that start their rows at different rounds
     // (tools/mb_gemv_rot.py, profiles/gemv_rot_sweep.jsonl): down_proj, the split-q step's k|v and q rows of q|k|v, o_proj and lm_head; gate|up does not gain and
     // stays plain.  Same bits as the plain weights through gemv2_body's ROT form.  Made at finalize() when the option is on (or when it is switched on later);
-    // load_weight re-packs a copy whose source it has just rewritten.  Every other reader — prefill GEMMs, the decode batch, the three-launch decode form's
-    // q|k|v launch, the fp32 engine, training — keeps the plain tensors.  Steps 1 / 3 / 5 measure alike; 3 is the step of the first experiment.
+    // load_weight re-packs a copy whose source, or whose launch's fused norm, it has just rewritten.  Every other reader — prefill GEMMs, the decode batch, the
+    // three-launch decode form's q|k|v launch, the fp32 engine, training — keeps the plain tensors.  Steps 1 / 3 / 5 measure alike; 3 is the step of the first
+    // experiment.  A copy is laid out for the rows per wave of the launch that reads it, and nothing checks that at launch: so the packer takes them from the
+    // launch description itself (rot_rows: gemv_args of the site's DecLinear), never from a second statement of the shape.
     enum : int { kRotDown = 1, kRotKv = 2, kRotHead = 4, kRotQ = 8, kRotO = 16 };
     static constexpr int kRotStep = 3;
     static constexpr int rot_set = kRotDown | kRotKv | kRotHead | kRotQ | kRotO;     // linears that get a copy: all but gate|up (profiles/EXPERIMENTS.md)
     int rot_live = 0;                                              // ... of which this model's shapes take the hand-counted stream: set by ensure_rot_weights
     void* rot_lm_head = nullptr;
     void ensure_rot_weights(hipStream_t st);      // makes the copies that do not exist yet (idempotent)
-    void pack_rot(void*& dst, const void* W, const GemvArgs& launch, int R, hipStream_t st);
+    int rot_rows(DecSite site, const DecLinear& d) const;      // rows per wave of the decode launch that reads the site's rotated copy
+    void pack_rot(void*& dst, DecSite site, const DecLayerW* w, hipStream_t st);      // (re)packs one site's copy into dst, once its source exists
     void pack_rot_layer(DecLayerW& w, int which, hipStream_t st);      // (re)packs the copies `which` (kRot* bits) of one layer, as far as they are live
     void pack_rot_head(hipStream_t st);
-    // the GemvArgs of a decode linear on its rotated copy, when the option is on and the copy exists
-    GemvArgs rot_args(GemvArgs g, const void* packed, int step) const {
-        if (opt_rot && packed) { g.W = packed; g.ldw = gemv_rot_pitch(g.K); g.rot = step; }
-        return g;
-    }
     void ensure_batch_weights(hipStream_t st);      // second, fragment-order copy of the decoder weights (first Batch pays for it)
     std::vector<DecLayerW> dec;
     void *v_cls = nullptr, *v_patch_w = nullptr, *v_pos = nullptr, *v_pre_w = nullptr, *v_pre_b = nullptr;

@@ -796,15 +796,17 @@ bool gemv2_applies(int dtype, const GemvArgs& a) {
 // of round 3 (tools/mb_decode.py, LLaVA-1.5-7B, per launch incl. ~1.4 us of event pair; gemv_kernel -> gemv2_kernel): q|k|v 20.5 -> 19.1 us (R 2, P 4),
 // gate|up 30.9 -> 29.5 (2, 4), down 19.9 -> 17.8 (1, 8: K = 11008 keeps 8 KB per wave on the wire), lm_head 45.8 -> 42.2 (2, 4), o_proj 8.7 -> 8.8 (1, 2).
 // The rule in one place: 0 = (2, 4), 1 = (1, 8), 2 = (1, 2).  (The rotated copy of a weight is laid out for the R of its launch: gemv2_rows_per_wave.)
-static int gemv2_rp(const GemvArgs& a) {
-    if (a.act == kActSiluMul) return 0;
-    if (a.K >= 8192) return 1;
+static int gemv2_rp(int N, int K, bool fused_norm, int act) {
+    if (act == kActSiluMul) return 0;
+    if (K >= 8192) return 1;
     // small linears (<= 32 M weights): o_proj keeps one row per wave (1024 short-lived workgroups); with the RMSNorm fused — the split-q step's q projection — every
     // workgroup also normalises the whole input row, so half as many workgroups with two rows per wave win: 8.1 -> 7.5 us (profiles/r05_small_gemv_rp.txt)
-    if ((size_t)a.N * a.K <= ((size_t)1 << 25)) return a.norm_w ? 0 : 2;
+    if ((size_t)N * K <= ((size_t)1 << 25)) return fused_norm ? 0 : 2;
     return 0;
 }
-int gemv2_rows_per_wave(const GemvArgs& a) { return gemv2_rp(a) == 0 ? 2 : 1; }
+static int gemv2_rp(const GemvArgs& a) { return gemv2_rp(a.N, a.K, a.norm_w != nullptr, a.act); }
+int gemv2_rows_per_wave(int N, int K, bool fused_norm, int act) { return gemv2_rp(N, K, fused_norm, act) == 0 ? 2 : 1; }
+int gemv2_rows_per_wave(const GemvArgs& a) { return gemv2_rows_per_wave(a.N, a.K, a.norm_w != nullptr, a.act); }
 
 template <typename T>
 static bool launch_gemv2(const GemvArgs& a, hipStream_t st) {

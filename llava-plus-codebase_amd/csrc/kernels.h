@@ -76,7 +76,8 @@ bool gemv2_applies(int dtype, const GemvArgs& a);
 // zero-filled past K); row n belongs to wave slot s = n / R (R = gemv2_rows_per_wave of the launch that will read it; with the SiLU.mul row pairing: the slot of
 // the wave that reads row n) and its physical round p holds logical round (p - (s * rot) % NR + NR) % NR.  Same bits out of the GEMV, another walk over memory.
 inline int gemv_rot_pitch(int K) { return ((K / 8 + 63) / 64) * 512; }
-int gemv2_rows_per_wave(const GemvArgs& a);       // rows per wave launch_gemv(MB = 1) gives this shape on the hand-counted stream (N, K, act, norm_w are read)
+int gemv2_rows_per_wave(int N, int K, bool fused_norm, int act);      // rows per wave launch_gemv(MB = 1) gives this shape on the hand-counted stream
+int gemv2_rows_per_wave(const GemvArgs& a);       // ... of a launch: (a.N, a.K, a.norm_w != null, a.act)
 void launch_gemv_rot_pack(int dtype, const void* W, int ldw, void* dst, int N, int K, int R, int rot, bool silu, hipStream_t st);
 
 // ---- attention (attention.hip) ------------------------------------------------------------------------------
@@ -181,6 +182,9 @@ struct DecAttnArgs {
 void launch_decode_attn_step(int dtype, int D, const DecAttnArgs& a, hipStream_t st);
 // split-q decode step: ONE launch = the attention workgroups (q from the row a preceding launch wrote) + the k|v projection g (C unused: its rows leave as
 // granules); g = rows [nh D, (nh + 2 nkv) D) of the fused q|k|v weight with the RMSNorm fused as in the plain projection.  See decode_attn.hip.
+// The projection part runs kDecodeKvRowsPerWave rows per wave (decode_kv_attn_kernel's gemv2_body form): the launcher's grid and the layout of a rotated copy of
+// the k|v rows both follow from it.
+constexpr int kDecodeKvRowsPerWave = 2;
 bool decode_kv_attn_applies(int dtype, int D, const GemvArgs& g);
 int decode_kv_attn_resident_slots(int dtype, int D, int K);      // occupancy x CUs of the split-q launch on the current device
 void launch_decode_kv_attn(int dtype, int D, const DecAttnArgs& a, const GemvArgs& g, hipStream_t st);
